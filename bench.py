@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: point-flow forward + log-det throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload airplane|m1|ae|svr|k16|k16_b1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload airplane|m1|ae|svr|k16|k16_b1] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic clouds that are already resident in
 HBM: for every mixture component, the FiLM kernel + the fused coupling-stack kernel (inverse direction,
@@ -13,7 +13,10 @@ fixed (weak scaling), no data-path collective; started either by the
 torch.distributed.run ... bench.py --gpus N` or, when no launcher environment is present, by bench.py itself
 (`python bench.py --gpus N` spawns the N ranks before touching the GPU, like the reference's mp.spawn in train_ae.py:183-193).
 
-Prints ONE JSON line on rank 0: the BASELINE metric on configs[1] (`value`), `roofline` of the dominant kernel against
+Prints ONE JSON line on rank 0: the BASELINE metric on configs[1] (`value`) and `ms_per_step`, the wall time of one timed step.
+A plain run does only that: set up, warm up, time K steps, print the line.  `--dump-outputs DIR` then also writes the arrays the
+timed path returned in its last step (rank 0's shard) as DIR/<name>.npy, float32; the inputs are seeded, so two builds can be
+compared output for output.  With `--full` the line also carries `roofline` of the dominant kernel against
 the unit that executes it (kernel duration from HIP events around the launch; `traffic` = HBM-side bytes per launch measured by two
 `rocprofv3 --pmc` child passes of this script, N = 1 only: headline and `also.m1`, null elsewhere), `also` = the other BASELINE shapes
 (m1, ae, svr, k16, k16_b1) timed by the same protocol in the same run plus the whole training step (`train_step`: children of this
@@ -63,6 +66,23 @@ MFMA_F16_PEAK_TFLOPS = 2500.0  # dense f16/bf16 MFMA peak; the contraction runs 
 def flops_per_point(L, f):
     """Algorithmic flop per point per component: C*(4f^2 + 12f), unpadded f."""
     return 3 * L * (4 * f * f + 12 * f)
+
+
+DUMP_BYTES = 64_000_000 - 4096      # --dump-outputs budget for all arrays together (room left for the .npy headers)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: array} as out_dir/<name>.npy in float32 (float64 stays float64).  An array larger than its equal share of
+    DUMP_BYTES is replaced by a fixed, seeded sample of its elements (flattened, in index order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > share:
+            n = share // a.itemsize
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def host_cores():
@@ -242,8 +262,11 @@ def spawn_ranks(args, argv):
     return subprocess.run(cmd, env=env).returncode
 
 
-def run_workload(name, args, dev, rank, world, sync_all, reduce_max):
-    """Build one workload, time `args.steps` steps of it after `args.warmup` warm-up steps; -> dict of measurements."""
+def workload_inputs(name, dev, rank=0):
+    """The seeded state and inputs of one workload on `dev`, the same in every run: -> (decoders, p, g, nll_args).  Every rank
+    owns its own shard of shapes.  Density workloads with K > 1 end in the fused mixture NLL, as the training loss consumes them
+    (SURVEY 8d, shape M2): nll_args = synthetic base Gaussians and mixture logits (mu0, lv0, logits), resident like the inputs;
+    None for the other workloads."""
     cfg = WORKLOADS[name]
     K, L, f, G, B, N, mode = (cfg[k] for k in ('K', 'L', 'f', 'G', 'B', 'N', 'mode'))
     decoders = []
@@ -251,28 +274,36 @@ def run_workload(name, args, dev, rank, world, sync_all, reduce_max):
         d = gw.LocalCondRNVPDecoder(L, f, G)
         load_synth_(d, 2 + k)
         decoders.append(d.to(dev).eval())
-    p, g = synth_inputs(B, N, G, 1000 * rank)          # every rank owns its own shard of shapes
+    p, g = synth_inputs(B, N, G, 1000 * rank)
     pd, gd = torch.from_numpy(p).to(dev), torch.from_numpy(g).to(dev)
-    eps = decoders[0].flows[0].nvp1._eps_value
-    sideways = mode == 'direct' and K > 1                # sampling: each point visits ONE component
-    stack = gw.MixtureStack(decoders)                    # K components: one FiLM launch + one stack launch
-    counts = [N // K] * K
-
-    # density workloads with K > 1 end in the fused mixture NLL, as the training loss consumes them (shape M2):
-    # synthetic base Gaussians and mixture logits, resident like the inputs
-    with_nll = (not sideways) and K > 1
-    if with_nll:
+    nll_args = None
+    if K > 1 and mode != 'direct':
         rng = np.random.default_rng(77 + rank)
         mu0 = torch.from_numpy((0.05 * rng.standard_normal((K, B, 3))).astype(np.float32)).to(dev)
         lv0 = torch.from_numpy((0.2 * rng.standard_normal((K, B, 3))).astype(np.float32)).to(dev)
         logits = torch.from_numpy(rng.standard_normal((B, K)).astype(np.float32)).to(dev)
+        nll_args = (mu0, lv0, logits)
+    return decoders, pd, gd, nll_args
+
+
+def run_workload(name, args, dev, rank, world, sync_all, reduce_max):
+    """Build one workload, time `args.steps` steps of it after `args.warmup` warm-up steps; -> dict of measurements, `outputs` =
+    {name: tensor} the last timed step returned.  `kern_ms` / `achieved` (the per-kernel probe) are measured only with --full."""
+    cfg = WORKLOADS[name]
+    K, L, f, G, B, N, mode = (cfg[k] for k in ('K', 'L', 'f', 'G', 'B', 'N', 'mode'))
+    decoders, pd, gd, nll_args = workload_inputs(name, dev, rank)
+    eps = decoders[0].flows[0].nvp1._eps_value
+    sideways = mode == 'direct' and K > 1                # sampling: each point visits ONE component
+    stack = gw.MixtureStack(decoders)                    # K components: one FiLM launch + one stack launch
+    counts = [N // K] * K
+    with_nll = nll_args is not None
 
     def launch_step():
         if sideways:
             return stack.forward_partition(pd, gd, counts, mode)
         z, ld = stack.forward_all(pd, gd, mode)
         if with_nll:
-            return z, ld, _lib.mixture_nll(z, ld, mu0, lv0, logits)
+            return z, ld, _lib.mixture_nll(z, ld, *nll_args)
         return z, ld
 
     probe_out = [torch.empty((B, 3, N) if sideways else (K, B, 3, N), device=dev) for _ in range(2)]
@@ -293,7 +324,7 @@ def run_workload(name, args, dev, rank, world, sync_all, reduce_max):
         if timers is not None:
             timers.append((e0, e1))
         if with_nll:
-            res = (*res, _lib.mixture_nll(res[0], res[1], mu0, lv0, logits))
+            res = (*res, _lib.mixture_nll(res[0], res[1], *nll_args))
         return res
 
     eager_step = step
@@ -326,13 +357,13 @@ def run_workload(name, args, dev, rank, world, sync_all, reduce_max):
 
     probe = []
     if graph is not None:
-        # per-kernel duration of the dominant kernel: same launches, same inputs, eager, HIP events around each stack launch
-        # on the launch stream (a graph replay cannot be bracketed per kernel).  Runs BEFORE the warm-up and the timed
+        # per-kernel duration of the dominant kernel (--full): same launches, same inputs, eager, HIP events around each stack
+        # launch on the launch stream (a graph replay cannot be bracketed per kernel).  Runs BEFORE the warm-up and the timed
         # region, so the timed steps also start from settled clocks whatever --warmup is.
         with torch.no_grad():
             for _ in range(100):            # ~50 ms of load: clocks settle before anything is measured
                 eager_step()
-            for _ in range(max(10, args.steps // 2)):
+            for _ in range(max(10, args.steps // 2) if args.full else 0):
                 eager_step(probe)
         torch.cuda.synchronize(dev)
 
@@ -344,7 +375,7 @@ def run_workload(name, args, dev, rank, world, sync_all, reduce_max):
         t0 = time.perf_counter()
         for _ in range(args.steps):
             # graph mode: no event records inside the timed region (the per-kernel probe ran before, eagerly)
-            step(timers if graph is None else None)
+            res = step(timers if graph is None else None)
         sync_all()
         elapsed = time.perf_counter() - t0
     elapsed = reduce_max(elapsed)
@@ -353,10 +384,11 @@ def run_workload(name, args, dev, rank, world, sync_all, reduce_max):
     pts_per_launch = B * N * comp_passes                                         # all components in one launch
     if graph is not None:
         timers = probe
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in timers]))           # one stack launch, HIP events
+    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in timers])) if timers else None      # one stack launch, HIP events
+    names = ('out', 'logdet', 'nll')[:len(res)]
     return dict(cfg=cfg, value=world * pts_per_launch * args.steps / elapsed / 1e6, elapsed=elapsed, kern_ms=kern_ms,
-                pts_per_launch=pts_per_launch, with_nll=with_nll,
-                achieved=flops_per_point(L, f) * pts_per_launch / (kern_ms * 1e-3) / 1e12)
+                pts_per_launch=pts_per_launch, with_nll=with_nll, outputs=dict(zip(names, res)),
+                achieved=flops_per_point(L, f) * pts_per_launch / (kern_ms * 1e-3) / 1e12 if kern_ms else None)
 
 
 def exact_fp32_record(name, m, dev, reps=10):
@@ -366,13 +398,7 @@ def exact_fp32_record(name, m, dev, reps=10):
     leave: no point of the bench grids is out of range).  HIP events around the launches alone, results in preallocated tensors."""
     cfg = WORKLOADS[name]
     K, L, f, G, B, N, mode = (cfg[k] for k in ('K', 'L', 'f', 'G', 'B', 'N', 'mode'))
-    decoders = []
-    for k in range(K):
-        d = gw.LocalCondRNVPDecoder(L, f, G)
-        load_synth_(d, 2 + k)
-        decoders.append(d.to(dev).eval())
-    p, g = synth_inputs(B, N, G, 0)
-    pd, gd = torch.from_numpy(p).to(dev), torch.from_numpy(g).to(dev)
+    decoders, pd, gd, _ = workload_inputs(name, dev)
     stack = gw.MixtureStack(decoders)
     eps = decoders[0].flows[0].nvp1._eps_value
     outs = [torch.empty(K, B, 3, N, device=dev) for _ in range(2)]
@@ -487,8 +513,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
-    ap.add_argument('--warmup', type=int, default=100)
+    ap.add_argument('--warmup', type=int, default=100,
+                    help='untimed steps before the timed ones; in graph mode (the default) 100 eager steps run before them '
+                         'as well, so that clocks have settled whatever this is')
     ap.add_argument('--workload', default='airplane', choices=sorted(WORKLOADS))
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: roofline (per-kernel probe, rocprofv3 traffic passes), '
+                         'the other shapes, exact fp32 and the training step (`also`), and cpu_baseline; the --no-* options '
+                         'below act within it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-live-traffic', action='store_true', help='skip the rocprofv3 --pmc child passes that measure roofline.traffic (it is then null)')
     ap.add_argument('--no-also', action='store_true', help='skip the secondary M1 (north-star shape) measurement')
@@ -505,6 +539,8 @@ def main():
     ap.add_argument('--lib', default=None, help='tuning hook: load this build of libgwtf_hip.so (A/B of two builds in one call)')
     ap.add_argument('--dry-run-spawn', action='store_true', help='print the launcher command instead of running it')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.lib:
         _lib.LIB_PATH = args.lib
 
@@ -541,8 +577,10 @@ def main():
         return float(t.item())
 
     m = run_workload(args.workload, args, dev, rank, world, sync_all, reduce_max)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v.detach().cpu().numpy() for k, v in m['outputs'].items()})
     also = None
-    if args.workload == 'airplane' and not args.no_also:
+    if args.full and args.workload == 'airplane' and not args.no_also:
         # the metric's own shape (B=32 x N=2048, the north-star module) and the other BASELINE configs' shapes, timed by the
         # same protocol in the same run (a few seconds each)
         also = {}
@@ -580,12 +618,14 @@ def main():
                        'sharding': f'batch of shapes over {world} rank(s), no data-path collective',
                        'launch': ('eager: ' if args.eager else 'one hipGraph replay per step: ') + '1 FiLM + 1 stack launch for all components'
                                  + (' + 1 mixture-NLL launch (per-shape NLL over K components)' if m['with_nll'] else '')},
-            # the default invocation measures the headline kernel's HBM traffic itself (never from inside another profiler)
-            'roofline': roofline_record(args.workload, m, live=(world == 1 and not args.no_live_traffic and also is not None and not under_profiler())),
         }
+        if args.full:
+            # --full on the airplane headline measures the headline kernel's HBM traffic itself (never from inside another profiler)
+            line['roofline'] = roofline_record(args.workload, m, live=(world == 1 and not args.no_live_traffic and also is not None
+                                                                         and not under_profiler()))
         if also is not None:
             line['also'] = also
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(cfg)
         print(json.dumps(line), flush=True)
     if dist is not None:

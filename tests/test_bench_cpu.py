@@ -19,6 +19,22 @@ def test_bench_spawns_its_own_ranks_when_no_launcher_is_present():
     assert cmd[i + 1:i + 3] == ['--gpus', '4'] and '--steps' in cmd[i:]
 
 
+def test_dump_outputs_keeps_float_types_and_samples_within_the_budget(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 4000)
+    arrays = {'small': np.arange(10, dtype=np.float16).reshape(2, 5), 'big': np.arange(3000, dtype=np.float64)}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    small = np.load(tmp_path / 'a' / 'small.npy')
+    assert small.dtype == np.float32 and small.shape == (2, 5) and np.array_equal(small, arrays['small'])
+    big = np.load(tmp_path / 'a' / 'big.npy')
+    assert big.dtype == np.float64 and big.nbytes <= 2000 and big.size == 250
+    assert np.all(np.diff(big) > 0) and np.all(np.isin(big, arrays['big']))        # a sample, in index order
+    assert np.array_equal(big, np.load(tmp_path / 'b' / 'big.npy'))                # the same sample every run
+
+
 def test_roofline_peak_is_the_executing_unit():
     sys.path.insert(0, ROOT)
     import bench

@@ -22,7 +22,7 @@ def _run(extra):
 
 
 def test_single_gpu_line_has_roofline_and_m1():
-    line = _run([])
+    line = _run(['--full'])
     assert line['n_gpus'] == 1 and line['value'] > 0 and line['scaling'] == 'weak'
     r = line['roofline']
     assert r['bound'] == 'mfma' and 0 < r['frac'] < 1 and abs(r['frac'] - r['achieved'] / r['peak']) < 1e-3
@@ -50,6 +50,33 @@ def test_single_gpu_line_has_roofline_and_m1():
     assert 'error' not in ae and 2 < ae['plain_ms_per_step'] <= ae['data_parallel_path_1rank_ms_per_step'] < 40, ae
 
 
+def test_plain_line_is_lean_and_dumps_the_timed_outputs(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes what the last timed step returned, which is
+    what one eager call on the same seeded inputs (bench.workload_inputs, rank 0's shard of the airplane workload) computes."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    import go_with_the_flows_amd as gw
+    from go_with_the_flows_amd import _lib
+
+    line = _run(['--dump-outputs', str(tmp_path)])
+    assert {'metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'} <= set(line)
+    assert not {'roofline', 'also', 'cpu_baseline'} & set(line), sorted(line)
+    assert line['steps'] == 5 and line['ms_per_step'] > 0
+    cfg = bench.WORKLOADS['airplane']
+    assert abs(line['value'] - cfg['K'] * cfg['B'] * cfg['N'] / (line['ms_per_step'] * 1e-3) / 1e6) / line['value'] < 1e-2
+    decoders, p, g, nll_args = bench.workload_inputs('airplane', torch.device('cuda', 0))
+    with torch.no_grad():
+        z, ld = gw.MixtureStack(decoders).forward_all(p, g, 'inverse')
+        nll = _lib.mixture_nll(z, ld, *nll_args)
+    assert sorted(os.listdir(tmp_path)) == ['logdet.npy', 'nll.npy', 'out.npy']
+    for name, ref in (('out', z), ('logdet', ld), ('nll', nll)):
+        got = np.load(tmp_path / (name + '.npy'))
+        assert got.dtype == np.float32 and got.shape == tuple(ref.shape), (name, got.dtype, got.shape)
+        np.testing.assert_allclose(got, ref.cpu().numpy(), rtol=1e-6, atol=1e-6, err_msg=name)
+
+
 def test_gpus_2_spawns_itself_and_reports_the_aggregate():
     line = _run(['--gpus', '2', '--backend', 'gloo', '--share-device', '--no-also'])
     assert line['n_gpus'] == 2 and line['value'] > 0
@@ -61,7 +88,7 @@ def test_gpus_2_spawns_itself_and_reports_the_aggregate():
 def test_gpus_2_training_step_record_rehearsal():
     """bench.py --gpus 2 also times the data-parallel training step (one child per rank, the children form their own group):
     rehearsed on the one card over gloo (eager step: gloo's collectives are host-side, nothing to capture)."""
-    line = _run(['--gpus', '2', '--backend', 'gloo', '--share-device', '--also-select', 'train_step', '--train-step-steps', '2'])
+    line = _run(['--full', '--gpus', '2', '--backend', 'gloo', '--share-device', '--also-select', 'train_step', '--train-step-steps', '2'])
     ts = line['also']['train_step']
     for label, b in (('global_batch_64', 32), ('per_rank_batch_64', 64)):
         assert 'error' not in ts[label] and ts[label]['per_rank_batch'] == b and ts[label]['ms_per_step'] > 0, ts
