@@ -46,7 +46,15 @@ __global__ __launch_bounds__(1024) void nll_kernel(const float* __restrict__ z, 
   float local = 0.f;
   const int n_end = min(N, (int)(blockIdx.x + 1) * ppb);
   for (int n = blockIdx.x * ppb + threadIdx.x; n < n_end; n += blockDim.x) {
-    float m = -INFINITY, s = 0.f;  // online log-sum-exp over components
+    // Online log-sum-exp over components.  A component whose log weight underflowed to -inf (logf(expf(logit)) with the logit
+    // below ~-104, the reference's quirk) adds exp(-inf) = 0 and is skipped: rescaling by expf(m - lp) would be expf(-inf + inf) = NaN
+    // when it comes first.  Every component -inf: m = -inf, s = 0, lse = -inf and the shape's NLL is +inf, as in fp32 torch of the
+    // reference.  The library is built with -fno-honor-nans: infinities are honoured, so the test against -INFINITY is sound, but
+    // NaN is not -- the compiler may rewrite the comparisons and the expf range checks so that a NaN lp adds 0 to s.  A NaN is
+    // therefore caught on the bits of lp, made opaque to the optimiser (it would otherwise fold the test away: lp comes from no-NaN
+    // arithmetic), and a NaN anywhere makes the point's lse -- hence the shape's NLL -- NaN.
+    float m = -INFINITY, s = 0.f;
+    bool nan_seen = false;
     for (int k = 0; k < K; ++k) {
       float qsum = 0.f;
 #pragma unroll
@@ -55,7 +63,10 @@ __global__ __launch_bounds__(1024) void nll_kernel(const float* __restrict__ z, 
         const float diff = z[o] - s_mu[k][d];
         qsum += (s_lv[k][d] + logdet[o]) + diff * diff * s_iv[k][d];
       }
-      const float lp = -0.5f * qsum - half_log2pi3 + s_logw[k];
+      float lp = -0.5f * qsum - half_log2pi3 + s_logw[k];
+      asm volatile("" : "+v"(lp));
+      nan_seen |= (__float_as_uint(lp) & 0x7fffffffu) > 0x7f800000u;
+      if (lp == -INFINITY) continue;
       if (lp > m || k == 0) {
         s = s * expf(m - lp) + 1.0f;
         m = lp;
@@ -63,7 +74,7 @@ __global__ __launch_bounds__(1024) void nll_kernel(const float* __restrict__ z, 
         s += expf(lp - m);
       }
     }
-    const float lse = m + logf(s);
+    const float lse = nan_seen ? __uint_as_float(0x7fc00000u) : m + logf(s);
     if (point_lse) point_lse[(size_t)b * N + n] = lse;
     local += lse;
   }

@@ -33,3 +33,23 @@ def state64(st):
 
 def maxabs(a, b):
     return float(np.max(np.abs(np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64))))
+
+
+def mixture_nll_torch(z, logdet, mu0, lv0, logits, quirk=False):
+    """The reference's FlowMixtureNLL (losses.py:88-137) written literally in torch ops, in the inputs' dtype: -> (per-shape
+    NLL (B,), per-point lse (B,N), per-component log-density lp (K,B,N), log weights (B,K)).  z, logdet (K,B,3,N); mu0, lv0
+    (K,B,3); logits (B,K).  quirk: log w = log(exp(logit)) - logsumexp(logits) as the reference computes it in fp32, where a
+    logit below ~-104 underflows to log w = -inf (the component drops out of the mixture).  In fp32 that is the literal formula;
+    in float64, where exp(-200) does not underflow, the same -inf is applied explicitly, so the float64 run computes the
+    function the fp32 reference computes.  Without quirk, log w = logit - logsumexp(logits)."""
+    lse_w = torch.logsumexp(logits, dim=-1, keepdim=True)
+    if not quirk:
+        logw = logits - lse_w                                                                                  # (B,K)
+    elif logits.dtype == torch.float32:
+        logw = torch.log(torch.exp(logits)) - lse_w
+    else:
+        logw = torch.where(torch.exp(logits.float()) == 0, float('-inf'), logits - lse_w)
+    lp = -0.5 * ((lv0[..., None] + logdet) + (z - mu0[..., None]) ** 2 / torch.exp(lv0[..., None])).sum(2) \
+        - 0.5 * 3 * np.log(2 * np.pi)                                                                          # (K,B,N)
+    lse = torch.logsumexp(lp + logw.t()[:, :, None], dim=0)                                                    # (B,N)
+    return -lse.sum(-1), lse, lp, logw

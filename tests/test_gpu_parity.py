@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from conftest import golden, TOL_COORD, TOL_LOGDET, TOL_NLL_REL, tol_at_depth, record_parity
-from helpers import decoder_and_state, coupling_and_state, triple_and_state, state64, maxabs
+from helpers import decoder_and_state, coupling_and_state, triple_and_state, state64, maxabs, mixture_nll_torch
 import go_with_the_flows_amd as gw
 from go_with_the_flows_amd import _lib
 from go_with_the_flows_amd.synth import synth_inputs
@@ -786,10 +786,7 @@ def test_mixture_nll_backward_vs_torch_autograd():
     D = golden('g5_losses')
     L, f, G, B, N, K = D['dims']
     leaves_c = [torch.from_numpy(D[k]).clone().requires_grad_(True) for k in ('z', 'logdet', 'mu0', 'lv0', 'logits')]
-    zc, ldc, m0c, l0c, lgc = leaves_c
-    logw = lgc - torch.logsumexp(lgc, dim=-1, keepdim=True)                                   # (B,K)
-    lp = -0.5 * ((l0c[..., None] + ldc) + (zc - m0c[..., None]) ** 2 / torch.exp(l0c[..., None])).sum(2) - 0.5 * 3 * np.log(2 * np.pi)                                                        # (K,B,N)
-    ref = (-(torch.logsumexp(lp + logw.t()[:, :, None], dim=0)).sum(-1)).mean()
+    ref = mixture_nll_torch(*leaves_c)[0].mean()
     ref.backward()
     leaves = [dev(D[k]).requires_grad_(True) for k in ('z', 'logdet', 'mu0', 'lv0', 'logits')]
     pnll, per_shape = gw.flow_mixture_nll(*leaves)
