@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GWTF_LIB') or os.path.join(_HERE, 'libgwtf_hip.so')      # GWTF_LIB: an A/B build (tools/ab_build.sh)
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 MODE_DIRECT, MODE_INVERSE = 0, 1
 STAT_REPLICAS = 64   # GWTF_STAT_REPLICAS in csrc/gwtf_layout.h
@@ -129,6 +129,9 @@ _SIGNATURES = {
                                  [ctypes.c_int] * 3 + [_c_fp]),
     'gwtf_head_pair_forward': (ctypes.c_int, [_c_fp] * 9 + [ctypes.c_int] * 4 + [_c_fp]),
     'gwtf_head_pair_backward': (ctypes.c_int, [_c_fp] * 18 + [ctypes.c_int] * 4 + [_c_fp]),
+    'gwtf_resnet_packed_floats': (ctypes.c_size_t, [ctypes.c_int]),
+    'gwtf_resnet_work_floats': (ctypes.c_size_t, [ctypes.c_int] * 4),
+    'gwtf_resnet_forward': (ctypes.c_int, [_c_fp] * 4 + [ctypes.c_int] * 5 + [_c_fp]),
 }
 
 PHASE_FWD_INIT, PHASE_FWD_A, PHASE_FWD_B, PHASE_BWD_A, PHASE_BWD_B, PHASE_BWD_C = range(6)

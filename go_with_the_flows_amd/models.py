@@ -10,8 +10,10 @@ Besides the reference-shaped API there is the path a training loop should use: `
 the encoder (fused HIP kernel in eval), the prior flow, ONE batched launch for the K decoders and returns the tensors
 ``Flow_Mixture_Loss.fused`` reduces with the mixture-NLL kernel -- no 9*n_flows lists, no B x K Python loop.
 
-The image-conditioned variant (Flow_Mixture_SVR_Model, flow_mixture.py:181-239) is not mirrored: its ResNet-18 image
-encoder is convolutional work outside the point-flow path (out of scope).
+The image-conditioned variant, Flow_Mixture_SVR_Model (flow_mixture.py:181-230, single-view reconstruction), is mirrored the
+same way: its 4-channel ResNet-18 image encoder (resnet.py) runs on the HIP kernels of csrc/gwtf_resnet.hip in eval mode and
+on the library modules in train mode; the image's features give the prior flow its per-shape base Gaussian (``g0_prior``).
+``reconstruct_many`` is its batched evaluation path (S images -> S clouds, one partitioned decoder launch).
 """
 import math
 import os
@@ -24,6 +26,7 @@ from .decoders import LocalCondRNVPDecoder
 from .encoders import FeatureEncoder, PointNetCloudEncoder, WeightsEncoder
 from .mixture import MixtureStack, flow_mixture_nll
 from .prior import GaussianEntropy, GaussianFlowNLL, GlobalRNVPDecoder
+from .resnet import resnet18
 
 
 class Local_Cond_RNVP_MC_Global_RNVP_VAE(nn.Module):
@@ -392,6 +395,83 @@ class Flow_Mixture_Model(Local_Cond_RNVP_MC_Global_RNVP_VAE):
         zp.scatter_(2, slot_t.unsqueeze(1).expand(S, 3, n), z0.float())
         xp, _ = self.mixture_stack().forward_partition(zp, g_samples, [int(c) for c in counts], mode='direct')
         return xp.gather(2, slot_t.unsqueeze(1).expand(S, 3, n))
+
+
+class Flow_Mixture_SVR_Model(Flow_Mixture_Model):
+    """Single-view reconstruction (reference flow_mixture.py:181-230): an image encoder and a Gaussian head give the prior flow a
+    per-shape base distribution.  'training': the posterior comes from the cloud and runs through the prior flow inverse (its
+    base is the image's Gaussian); 'reconstruction': the image's base mean runs through the prior flow direct (no draw).
+    ``model.mode`` may be switched at run time (training.py:274)."""
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        G = self.g_latent_space_size
+        self.img_encoder = resnet18(num_classes=G)
+        self.g_prior_n_layers = kwargs.get('g_prior_n_layers')
+        self.g0_prior = FeatureEncoder(self.g_prior_n_layers, G, G, deterministic=False, mu_weight_std=0.0033, mu_bias=0.0,
+                                       logvar_weight_std=0.033, logvar_bias=0.0)
+        # the base class's learned global base Gaussian is replaced by the per-image one: out of the state_dict, as in the reference
+        self.g0_prior_mus = None
+        self.g0_prior_logvars = None
+
+    def encode(self, g_input, images, defer_prior=False):
+        """flow_mixture.py:199-230 -> the encoder dict; lists are ordered base -> data.  No '_g0_params': the base is per row, so
+        the loss takes its list path (the fused latent-loss kernel assumes one base Gaussian for the batch)."""
+        if images is None:
+            raise ValueError('Flow_Mixture_SVR_Model.encode needs images')
+        if self.mode not in ('training', 'reconstruction'):
+            raise ValueError(f'unknown util_mode {self.mode!r} for single-view reconstruction '
+                             "(expected 'training' or 'reconstruction')")
+        out = {}
+        mus, logvars = self.g0_prior(self.img_encoder(images))
+        out['g_prior_mus'], out['g_prior_logvars'] = [mus], [logvars]
+        if self.mode == 'training':
+            out['g_posterior_mus'], out['g_posterior_logvars'] = self.g_posterior(self._pooled_features(g_input))
+            out['g_posterior_samples'] = self.reparameterize(out['g_posterior_mus'], out['g_posterior_logvars'])
+            if defer_prior and hasattr(self.g_prior, 'forward_async'):
+                out['_prior_handle'] = self.g_prior.forward_async(out['g_posterior_samples'], mode='inverse')
+                return out
+            buf_g = self.g_prior(out['g_posterior_samples'], mode='inverse')
+            from .prior import stacked_lists
+            stacked = stacked_lists(self.g_prior)
+            if stacked is not None:
+                out['_g_prior_logvars_stacked'] = stacked[2]
+            out['g_prior_samples'] = buf_g[0] + [out['g_posterior_samples']]
+        else:
+            out['g_prior_samples'] = [mus]
+            buf_g = self.g_prior(mus, mode='direct')
+            out['g_prior_samples'] += buf_g[0]
+        out['g_prior_mus'] += buf_g[1]
+        out['g_prior_logvars'] += buf_g[2]
+        return out
+
+    def forward(self, g_input, p_input, images=None, n_sampled_points=None, labeled_samples=False, warmup=False):
+        """models.py:224-265 with the image branch taken."""
+        if self.mode not in ('training', 'reconstruction'):
+            raise ValueError(f'unknown util_mode {self.mode!r} for single-view reconstruction '
+                             "(expected 'training' or 'reconstruction')")
+        size = p_input.shape[2] if n_sampled_points is None else n_sampled_points
+        output_encoder = self.encode(g_input, images, defer_prior=self.mode == 'training')
+        g_sample = (output_encoder['g_posterior_samples'] if self.mode == 'training'
+                    else output_encoder['g_prior_samples'][-1])
+        if labeled_samples:
+            samples, labels, logits = self.decode(p_input, g_sample, size, labeled_samples, warmup)
+            return self.finish_encode(output_encoder), samples, labels, logits
+        output_decoder, logits = self.decode(p_input, g_sample, size, labeled_samples, warmup)
+        return self.finish_encode(output_encoder), output_decoder, logits
+
+    def forward_fused(self, g_input, p_input, warmup=False):
+        raise NotImplementedError('Flow_Mixture_SVR_Model trains through forward + Flow_Mixture_Loss (the list path)')
+
+    @torch.no_grad()
+    def reconstruct_many(self, images, n_points, return_labels=False):
+        """S images -> S clouds (the reference reconstructs one image per call, evaluating.py:94-96): the image encoder on all S
+        (HIP in eval mode), the g0_prior means through the prior flow direct, then ``sample_many``'s partitioned decoder launch.
+        Component draws are taken sample by sample (np.random.choice), in the order S calls of ``forward`` with B = 1 take them.
+        -> (S, 3, n_points)[, labels (S, n_points) in 1..K]."""
+        mus, _ = self.g0_prior(self.img_encoder(images))
+        g = self.g_prior(mus, mode='direct')[0][-1]
+        return self.sample_many(g, n_points, return_labels)
 
 
 def _restack(tensors):

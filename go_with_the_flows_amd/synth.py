@@ -55,6 +55,19 @@ def synth_state(template_state, seed, output_gain=1.0):
             v = rng.uniform(-1.0, 1.0, shape) / np.sqrt(shape[-1])
         elif name.endswith('film_w1') or name.endswith('film_b1') or name in ('mu_mlp0', 'logvar_mlp0', 'mu_mlp1', 'logvar_mlp1'):
             v = rng.normal(0.0, 0.08, shape) if kind == 'weight' else rng.normal(0.0, 0.1, shape)
+        elif name in ('conv1', 'conv2') or key.endswith('downsample.0.weight'):         # image encoder convolutions: He-scaled
+            v = rng.normal(0.0, np.sqrt(2.0 / np.prod(shape[1:])), shape)
+        elif name in ('bn1', 'bn2') or key.endswith('downsample.1.' + kind):             # image encoder BatchNorm2d
+            if kind == 'weight':
+                v = rng.uniform(0.6, 1.4, shape)
+            elif kind == 'bias':
+                v = rng.normal(0.0, 0.1, shape)
+            elif kind == 'running_mean':
+                v = rng.normal(0.0, 0.15, shape)
+            else:
+                v = rng.uniform(0.5, 1.5, shape)
+        elif name == 'fc':                                                                   # image encoder head
+            v = rng.uniform(-1.0, 1.0, shape) * np.sqrt(3.0 / shape[-1]) if kind == 'weight' else rng.normal(0.0, 0.1, shape)
         else:
             raise KeyError(f'synth_state: unknown parameter kind {key}')
         out[key] = np.asarray(v, dtype=np.int64 if kind == 'num_batches_tracked' else np.float32)
@@ -74,3 +87,53 @@ def synth_inputs(B, N, G, seed):
     p = (0.3 * rng.standard_normal((B, 3, N))).astype(np.float32)
     g = rng.standard_normal((B, G)).astype(np.float32)
     return p, g
+
+
+def synth_images(B, H, W, seed):
+    """Normalised 4-channel images ~ N(0,1) (the reference standardises each channel: config_SVR.yaml image_means / image_stds)."""
+    return np.random.default_rng(seed).standard_normal((B, 4, H, W)).astype(np.float32)
+
+
+def image_encoder_bn_names(encoder):
+    """Names (state_dict prefixes) of every BatchNorm of an image encoder, in state_dict order."""
+    return [n for n, m in encoder.named_modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+
+
+def calibrate_image_encoder(encoder, seed, n=8, H=64, W=64):
+    """Running statistics that keep eval-mode activations O(1) through the 8 blocks (synth_state's draws do not: with random
+    statistics a deep residual stack drifts by orders of magnitude and an absolute tolerance means nothing).  One train-mode
+    pass of a float64 CPU copy over synth_images(n, H, W, seed) with cumulative averaging: each BatchNorm's running statistics
+    become the batch statistics of its input.  Returns {'<bn>.running_mean' / '<bn>.running_var': float32 array}; load them
+    with load_image_encoder_stats_."""
+    import copy
+    enc = copy.deepcopy(encoder).cpu().double().train()
+    for m in enc.modules():
+        if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
+            m.momentum = None
+            m.reset_running_stats()
+    with torch.no_grad():
+        enc.forward_torch(torch.from_numpy(synth_images(n, H, W, seed)).double())
+    out = {}
+    for name in image_encoder_bn_names(enc):
+        m = enc.get_submodule(name)
+        out[name + '.running_mean'] = m.running_mean.float().numpy().copy()
+        out[name + '.running_var'] = m.running_var.float().numpy().copy()
+    return out
+
+
+def load_image_encoder_stats_(encoder, stats):
+    """Copy calibrated running statistics (calibrate_image_encoder, or a fixture's copy of them) into ``encoder`` in place."""
+    with torch.no_grad():
+        for key, v in stats.items():
+            name, kind = key.rsplit('.', 1)
+            buf = getattr(encoder.get_submodule(name), kind)
+            buf.copy_(torch.as_tensor(np.asarray(v)).to(buf.dtype))
+
+
+def conditioned_image_encoder_(encoder, seed, calib_seed=None):
+    """synth_state weights + calibrated running statistics (the state the image-encoder tolerances are asserted on).
+    Returns the statistics."""
+    load_synth_(encoder, seed)
+    stats = calibrate_image_encoder(encoder, seed + 1 if calib_seed is None else calib_seed)
+    load_image_encoder_stats_(encoder, stats)
+    return stats

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define GWTF_ABI_VERSION 6
+#define GWTF_ABI_VERSION 7
 #define GWTF_E_BADARG 10001   /* shape / mode / width outside what the kernels support */
 #define GWTF_E_UNSUPPORTED 10002   /* a layer-width list no kernel instantiation was built for */
 #define GWTF_MODE_DIRECT 0    /* sampling direction  base -> data (reference models.py:202) */
@@ -586,6 +586,31 @@ int gwtf_head_pair_backward(const float* x, const float* Wa, const float* bias_a
                             const float* ypre_a, const float* out_a, const float* ypre_b, const float* out_b, const float* g_out_a,
                             const float* g_out_b, float* g_y_a, float* g_y_b, float* g_x, float* g_Wa, float* g_bias_a, float* g_Wb,
                             float* g_bias_b, int B, int Din, int Dout_a, int Dout_b, void* stream);
+
+/* Image encoder of the single-view-reconstruction model (go_with_the_flows_amd/resnet.py): the 4-channel ResNet-18 of the
+ * reference's lib/networks/resnet.py:9-224 (BasicBlock x [2,2,2,2], fc -> fc_bn -> ReLU head), EVAL-MODE forward only
+ * (csrc/gwtf_resnet.hip).  Replaces img_encoder(images) in flow_mixture.py:212 for model.eval().
+ *   image   [B][4][H][W] NCHW fp32, H, W >= 32
+ *   packed  [gwtf_resnet_packed_floats(num_classes)], BatchNorm folded by the caller (float64 on the host, rounded once):
+ *           for each convolution in network order -- stem; then per block conv1, conv2 -- W [Cout][Kp] then shift [Cout], with
+ *           W[n][k] = weight[n][ci][kh][kw] * s[n], k = (kh * KW + kw) * Cin + ci, columns K..Kp-1 zero (Kp = K rounded up to
+ *           16; only the stem, K = 196, pads), s = gamma / sqrt(running_var + eps), shift = beta - running_mean * s.  The first
+ *           block of layer2..4 appends its downsample to conv2's rows: Kp = 9 * Cout + Cin, columns 9 Cout + ci = downsample
+ *           weight[n][ci] * s_ds[n], shift = shift_conv2 + shift_ds.  Then the head: W [num_classes][512] = fc.weight * s_fc,
+ *           bias [num_classes] = (fc.bias - running_mean) * s_fc + beta (fc_bn).
+ *   out     [B][num_classes]
+ *   work    [gwtf_resnet_work_floats(B, H, W, tune)] scratch (NHWC activations, split-K partial sums)
+ *   tune    GWTF_TUNE_RESNET_TILE(1: 64x64, 2: 32x32, 3: 64x32 output tile; 0: by shape) | GWTF_TUNE_RESNET_SPLIT(n: K split
+ *           in n parts, 1: none; 0: by shape).  Splits are summed in a fixed order: a launch is bit-identical to the last.
+ * gwtf_resnet_work_floats returns 0 for arguments gwtf_resnet_forward rejects (GWTF_E_BADARG). */
+#define GWTF_TUNE_RESNET_TILE(t) ((t) & 0xf)
+#define GWTF_TUNE_RESNET_SPLIT(n) (((n) & 0xff) << 4)
+#define GWTF_TUNE_RESNET_TILE_OF(w) ((w) & 0xf)
+#define GWTF_TUNE_RESNET_SPLIT_OF(w) (((w) >> 4) & 0xff)
+size_t gwtf_resnet_packed_floats(int num_classes);
+size_t gwtf_resnet_work_floats(int B, int H, int W, int tune);
+int gwtf_resnet_forward(const float* image, const float* packed, float* out, float* work, int B, int H, int W, int num_classes,
+                        int tune, void* stream);
 
 #ifdef __cplusplus
 }
