@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GWTF_LIB') or os.path.join(_HERE, 'libgwtf_hip.so')      # GWTF_LIB: an A/B build (tools/ab_build.sh)
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 MODE_DIRECT, MODE_INVERSE = 0, 1
 STAT_REPLICAS = 64   # GWTF_STAT_REPLICAS in csrc/gwtf_layout.h
@@ -28,10 +28,8 @@ _SIGNATURES = {
     'gwtf_film_out_floats': (ctypes.c_size_t, [ctypes.c_int]),
     'gwtf_pack_weights': (ctypes.c_int, [_c_fp, _c_fp, _c_fp] + [ctypes.c_int] * 5 + [_c_fp]),
     'gwtf_pack_weights_k': (ctypes.c_int, [_c_fp, _c_fp, _c_fp] + [ctypes.c_int] * 6 + [_c_fp]),
-    'gwtf_film_forward': (ctypes.c_int, [_c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_int, ctypes.c_float, ctypes.c_int, _c_fp]),
-    'gwtf_film_bn_swish_forward': (ctypes.c_int, [_c_fp] * 3 + [ctypes.c_long] * 3 + [ctypes.c_int] * 3 + [_c_fp] * 5),
-    'gwtf_film_bn_swish_backward': (ctypes.c_int, [_c_fp] * 4 + [ctypes.c_long] * 3 + [ctypes.c_int] * 3 + [_c_fp] * 6),
+    'gwtf_film_forward': (ctypes.c_int, [_c_fp, _c_fp, _c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_float, _c_fp]),
     'gwtf_stack_forward': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, _c_fp]),
     'gwtf_stack_forward_multi': (ctypes.c_int, [_c_fp] * 8 + [ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 6 +
                                  [ctypes.c_float, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, _c_fp]),
@@ -47,20 +45,10 @@ _SIGNATURES = {
     'gwtf_latent_loss_forward': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 3 + [ctypes.c_float] * 3 + [_c_fp]),
     'gwtf_latent_loss_backward': (ctypes.c_int, [_c_fp] * 10 + [ctypes.c_int] * 3 + [ctypes.c_float] * 3 + [_c_fp]),
     'gwtf_stack_plan': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]),
-    'gwtf_train_moments': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_train_fold0': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp, ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_train_stats': (ctypes.c_int, [_c_fp, _c_fp, _c_fp] + [ctypes.c_int] * 5 + [_c_fp]),
-    'gwtf_train_fold1': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_double, _c_fp, _c_fp, _c_fp] + [ctypes.c_int] * 5 + [_c_fp]),
-    'gwtf_train_apply': (ctypes.c_int, [_c_fp] * 10 + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_train_forward': (ctypes.c_int, [_c_fp] * 14 + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, _c_fp]),
     'gwtf_pack_w1t': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_train_coupling_backward': (ctypes.c_int, [_c_fp] * 21 + [ctypes.c_int] * 7 + [ctypes.c_float, ctypes.c_int, _c_fp]),
     'gwtf_packed_b_coupling_floats': (ctypes.c_size_t, [ctypes.c_int]),
     'gwtf_pack_folded': (ctypes.c_int, [_c_fp] * 5 + [ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_train_backward': (ctypes.c_int, [_c_fp] * 23 + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_int, _c_fp]),
-    'gwtf_coupling_backward': (ctypes.c_int, [_c_fp] * 11 + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_int, _c_fp]),
     'gwtf_coupling_backward_lists': (ctypes.c_int, [_c_fp] * 13 + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_int, _c_fp]),
-    'gwtf_stats_backward': (ctypes.c_int, [_c_fp] * 7 + [ctypes.c_int] * 4 + [_c_fp]),
     'gwtf_dw1_partials': (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     'gwtf_dw1_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 3),
     'gwtf_dw1_reduce_scratch_floats': (ctypes.c_size_t, [ctypes.c_int]),
@@ -85,14 +73,12 @@ _SIGNATURES = {
     'gwtf_enc_train_supported': (ctypes.c_int, [_c_fp, ctypes.c_int]),
     'gwtf_enc_train_units_floats': (ctypes.c_size_t, [ctypes.c_int]),
     'gwtf_enc_train_act_floats': (ctypes.c_size_t, [ctypes.c_int] * 3),
-    'gwtf_enc_train_pack': (ctypes.c_int, [_c_fp] * 3 + [ctypes.c_int, _c_fp]),
     'gwtf_enc_train_pack_all': (ctypes.c_int, [_c_fp] * 10),
     'gwtf_enc_train_xmoments': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_int, ctypes.c_int, _c_fp]),
     'gwtf_enc_train_fold0': (ctypes.c_int, [_c_fp, ctypes.c_double] + [_c_fp] * 5 + [ctypes.c_float, _c_fp, _c_fp, _c_fp]),
     'gwtf_enc_train_fold': (ctypes.c_int, [_c_fp, ctypes.c_int, ctypes.c_double] + [_c_fp] * 4 + [ctypes.c_float, _c_fp, _c_fp, _c_fp]),
     'gwtf_enc_train_forward': (ctypes.c_int, [ctypes.c_int] + [_c_fp] * 9 + [ctypes.c_int, ctypes.c_int, _c_fp]),
     'gwtf_enc_train_pool': (ctypes.c_int, [_c_fp] * 6 + [ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_enc_train_pack_matrix': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_int, ctypes.c_int, _c_fp]),
     'gwtf_enc_train_top_scatter': (ctypes.c_int, [_c_fp] * 7 + [ctypes.c_int, ctypes.c_int, _c_fp]),
     'gwtf_enc_train_backward_top': (ctypes.c_int, [_c_fp] * 10 + [ctypes.c_int, ctypes.c_int, _c_fp]),
     'gwtf_enc_train_top': (ctypes.c_int, [_c_fp] * 7 + [ctypes.c_int, _c_fp]),
@@ -230,39 +216,29 @@ def padded_width(f):
     return lib().gwtf_padded_width(f)
 
 
-def pack_weights(raw, C, f, G, training, pattern0=0, K=1, stack_only=False):
-    """Packed stack / FiLM weights of K concatenated stacks of C couplings each (raw: K*C coupling records).  stack_only (train
-    pipeline): the stack weights alone -- its FiLM heads read the raw arena in place; returns (pw, None)."""
+def pack_weights(raw, C, f, G, train, pattern0=0, K=1):
+    """Packed stack / FiLM weights of K concatenated stacks of C couplings each (raw: K*C coupling records).  train (the train
+    pipeline's packing): the stack weights alone -- its FiLM heads read the raw arena in place; returns (pw, None)."""
     L = lib()
-    pw = torch.empty(K * C * L.gwtf_packed_w_coupling_floats(f), device=raw.device, dtype=torch.float32)
-    if stack_only:
-        if raw.numel() != K * C * L.gwtf_raw_coupling_floats(f, G):
-            raise GwtfError(f'raw arena has {raw.numel()} floats, expected {K * C * L.gwtf_raw_coupling_floats(f, G)}')
-        with torch.cuda.device(raw.device):
-            check(L.gwtf_pack_weights_k(_ptr(raw, 'raw'), _ptr(pw, 'packed_w'), None, K, C, f, G, int(pattern0), 2, _stream(raw)))
-        return pw, None
-    pf = torch.empty(K * C * L.gwtf_packed_film_coupling_floats(f, G), device=raw.device, dtype=torch.float32)
     if raw.numel() != K * C * L.gwtf_raw_coupling_floats(f, G):
         raise GwtfError(f'raw arena has {raw.numel()} floats, expected {K * C * L.gwtf_raw_coupling_floats(f, G)}')
+    pw = torch.empty(K * C * L.gwtf_packed_w_coupling_floats(f), device=raw.device, dtype=torch.float32)
+    pf = None if train else torch.empty(K * C * L.gwtf_packed_film_coupling_floats(f, G), device=raw.device, dtype=torch.float32)
     with torch.cuda.device(raw.device):
         check(L.gwtf_pack_weights_k(_ptr(raw, 'raw'), _ptr(pw, 'packed_w'), _ptr(pf, 'packed_film'), K, C, f, G, int(pattern0),
-                                    int(bool(training)), _stream(raw)))
+                                    int(bool(train)), _stream(raw)))
     return pw, pf
 
 
-def film_forward(g, packed_film, C, f, eps, training, want_stats=False):
-    """eval: the (B,C,6FP+4) record the stack kernel consumes.  training: RAW FiLM {a,b} as (B,C,2,2,FP)."""
+def film_forward(g, packed_film, C, f, eps):
+    """The (B,C,6FP+4) FiLM record the stack kernel consumes (eval-mode BatchNorm)."""
     L = lib()
     B, G = g.shape
-    if training:
-        out = torch.empty(B, C, 2, 2, L.gwtf_padded_width(f), device=g.device, dtype=torch.float32)
-    else:
-        out = torch.empty(B, C, L.gwtf_film_out_floats(f), device=g.device, dtype=torch.float32)
-    stats = torch.empty(C, 2, 2, 2, f, device=g.device, dtype=torch.float32) if (training and want_stats) else None
+    out = torch.empty(B, C, L.gwtf_film_out_floats(f), device=g.device, dtype=torch.float32)
     with torch.cuda.device(g.device):
-        check(L.gwtf_film_forward(_ptr(g, 'g'), _ptr(packed_film, 'packed_film'), _ptr(out, 'film_out'),
-                                  _ptr(stats, 'bn_stats'), B, G, C, f, float(eps), int(bool(training)), _stream(g)))
-    return (out, stats) if want_stats else out
+        check(L.gwtf_film_forward(_ptr(g, 'g'), _ptr(packed_film, 'packed_film'), _ptr(out, 'film_out'), B, G, C, f, float(eps),
+                                  _stream(g)))
+    return out
 
 
 # ---- the exact-fp32 contraction body (csrc/gwtf_stack_exact.hip) ---------------------------------------------------------------
@@ -437,45 +413,6 @@ def mixture_nll(z, logdet, mu0, lv0, logits, want_point_lse=False):
                                  _ptr(logits, 'logits'), _ptr(plse, 'point_lse'), _ptr(nll, 'nll_shape'), K, B, N,
                                  _stream(z)))
     return (nll, plse) if want_point_lse else nll
-
-
-def train_forward(p, g, raw, C, f, G, pattern0, eps, mode, want_lists):
-    """Train-mode (batch-statistic BatchNorm) forward of one coupling stack on one rank, entirely in HIP: the FiLM heads with
-    batch statistics over the B latent rows (gwtf_film_forward, training=1), then fold0 -> stats -> fold1 -> apply per
-    coupling from ONE C call (csrc/gwtf_train.hip).  Data-parallel runs take autograd.train_density_forward_multi instead.
-    Returns out, logdet, lists, bn_batch (C,2,4,2,f) = {batch mean, unbiased batch var} of the 8 BatchNorms per
-    coupling (kind 0 sd0_bn, 1 sd1_bn, 2 film_w0_bn, 3 film_b0_bn; branch 0 logvar, 1 mu)."""
-    L = lib()
-    B, _, N = p.shape
-    dev = p.device
-    FP = L.gwtf_padded_width(f)
-    FS = L.gwtf_film_out_floats(f)
-    st = _stream(p)
-    if B < 2:
-        raise ValueError('train-mode BatchNorm needs more than 1 shape per batch (torch raises the same)')
-    with torch.cuda.device(dev):
-        pw, pf = pack_weights(raw, C, f, G, True, pattern0)
-        film_raw, fstats = film_forward(g, pf, C, f, eps, True, want_stats=True)
-        # a non-finite parameter anywhere in a branch record -> NaN FiLM scale -> NaN outputs (the kernels' v_max ReLU alone
-        # would turn e.g. a NaN sd0 weight into a zero activation; reference training.py:43-46 aborts on a NaN loss)
-        film_raw[:, :, :, 0] += (raw.view(C, 2, -1).sum(-1) * 0.0).view(1, C, 2, 1)
-        mom = torch.zeros(C + 1, STAT_REPLICAS * 16, device=dev, dtype=torch.float32)
-        ystats = torch.zeros(C, STAT_REPLICAS * 2 * FP * 2, device=dev, dtype=torch.float32)
-        bn_batch = torch.zeros(C, 2, 4, 2, f, device=dev, dtype=torch.float32)
-        film_rec = torch.empty(B, C, FS, device=dev, dtype=torch.float32)
-        xbuf = torch.empty(2, B, 3, N, device=dev, dtype=torch.float32)
-        logdet = torch.empty_like(p)
-        lists = torch.empty(3, C, B, 3, N, device=dev, dtype=torch.float32) if want_lists else None
-        lp = [lists[i].data_ptr() for i in range(3)] if want_lists else [None, None, None]
-        check(L.gwtf_train_forward(_ptr(p, 'p'), _ptr(raw, 'raw'), pw.data_ptr(), None, film_raw.data_ptr(), mom.data_ptr(),
-                                   ystats.data_ptr(), bn_batch.data_ptr(), film_rec.data_ptr(), xbuf.data_ptr(),
-                                   logdet.data_ptr(), lp[0], lp[1], lp[2], B, N, C, f, G, pattern0, float(eps),
-                                   _MODES[mode], _TUNE[0], st))
-        out = xbuf[(C - 1) & 1]
-        # per-shape FiLM BatchNorms: biased batch var -> unbiased
-        bn_batch[:, :, 2:4, 0, :] = fstats[:, :, :, 0, :]
-        bn_batch[:, :, 2:4, 1, :] = fstats[:, :, :, 1, :] * (B / (B - 1.0))
-    return out, logdet, lists, bn_batch
 
 
 def stack_plan(K, B, N, f, segments=None, word=None):

@@ -7,10 +7,9 @@ gwtf_train.hip).  What is O(f^2 + B*f*G) stays a small torch graph on views of O
 module parameters and the latent g to the quantities the kernels consume (BatchNorm folded into sd0 / sd1, FiLM heads ->
 per-shape {c, u}), so autograd carries the kernels' gradients to every reference parameter and to g.
 
-  * eval BatchNorm (running statistics):  StackDensityFn                      -- one fused forward, one backward launch per coupling
-  * train BatchNorm, any number of ranks: TrainMixtureFn                      -- the K-batched, phase-split C pipeline (gwtf_mtrain_*):
+  * eval BatchNorm (running statistics):  StackDensityFn  -- one fused forward, one backward launch per coupling
+  * train BatchNorm, any number of ranks: TrainMixtureFn  -- the K-batched, phase-split C pipeline (gwtf_mtrain_*):
                                           all K mixture components per launch, ONE packed statistic all-reduce per phase
-  * cross-check of the above:             MomentsFn / StatsFn / ApplyFn chain -- one autograd node per coupling (force_autograd_chain)
 
 Reference semantics: loss.backward() through LocalCondRNVPDecoder.forward, training.py:54.
 """
@@ -73,7 +72,7 @@ def _gather(engine, raw=None):
 
 
 def _gather_film(raw, C, f, G):
-    """The FiLM-head slices of _gather for a (stacked) arena holding C couplings in all: what _film_train reads."""
+    """The FiLM-head slices of _gather for a (stacked) arena holding C couplings in all (tests/test_gpu_film_heads.py reads them)."""
     rv = raw.reshape(C, 2, -1)
     o_film, FS = 8 * f + f * f, f * G + 5 * f + f * f
     films = rv[:, :, o_film:o_film + 2 * FS].reshape(C, 2, 2, FS)
@@ -223,188 +222,7 @@ def density_forward(engine, p, g, mode='inverse'):
     return out, logdet, (ps, mus, lvs)
 
 
-# ======================================================================================================================
-# Train mode: batch-statistic BatchNorm.  The statistics make every coupling depend on global reductions of its own
-# input, so the differentiable path is a chain of small autograd nodes per coupling (reference flows.py:27,30,62,65 under
-# model.train() + loss.backward()):
-#     x --MomentsFn(HIP)--> M --fold0(torch)--> W0f,c0f --StatsFn(HIP)--> S --fold1(torch)--> c,u --ApplyFn(HIP)--> x', lv
-# Autograd sums the three contributions to dL/dx (apply, statistics of y1, moments of x) and the two contributions to the
-# sd0/sd1 weights; each HIP node's backward is one launch of csrc/gwtf_bwd.hip (+ the dW1 GEMM).
-# ======================================================================================================================
-def _pack_single(W1, W0f, c0f, f):
-    L = _lib.lib()
-    dev = W1.device
-    pw = torch.empty(L.gwtf_packed_w_coupling_floats(f), device=dev, dtype=torch.float32)
-    pb = torch.empty(L.gwtf_packed_b_coupling_floats(f), device=dev, dtype=torch.float32)
-    w1, w0, c0 = W1.detach().contiguous(), W0f.detach().contiguous(), c0f.detach().contiguous()
-    with torch.cuda.device(dev):
-        _lib.check(L.gwtf_pack_folded(w1.data_ptr(), w0.data_ptr(), c0.data_ptr(), pw.data_ptr(), pb.data_ptr(), 1, f,
-                                      torch.cuda.current_stream(dev).cuda_stream))
-    return pw, pb
-
-
-class MomentsFn(torch.autograd.Function):
-    """x (B,3,N) -> the 9 first/second moments summed over all points {Sx0..2, Sx0x0, Sx0x1, Sx0x2, Sx1x1, Sx1x2, Sx2x2}."""
-
-    @staticmethod
-    def forward(ctx, x):
-        L = _lib.lib()
-        x = x.contiguous()
-        B, _, N = x.shape
-        mom = torch.zeros(_lib.STAT_REPLICAS, 16, device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            _lib.check(L.gwtf_train_moments(x.data_ptr(), mom.data_ptr(), B, N, _lib._stream(x)))
-        ctx.save_for_backward(x)
-        return mom.sum(0)[:9]
-
-    @staticmethod
-    def backward(ctx, gM):
-        (x,) = ctx.saved_tensors
-        Q = x.new_zeros(3, 3)
-        idx = [(0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)]
-        for k, (a, b) in enumerate(idx):
-            if a == b:
-                Q[a, a] = 2.0 * gM[3 + k]
-            else:
-                Q[a, b] = gM[3 + k]
-                Q[b, a] = gM[3 + k]
-        return gM[:3].view(1, 3, 1) + torch.einsum('ab,zbn->zan', Q, x)
-
-
-class StatsFn(torch.autograd.Function):
-    """S[branch][feature][{sum y1, sum y1^2}] over all points, y1 = sd1(relu(W0f x_keep + c0f))  (csrc: stats_kernel)."""
-
-    @staticmethod
-    def forward(ctx, x, W0f, c0f, W1, pw, pb, pat, f):
-        L = _lib.lib()
-        x = x.contiguous()
-        B, _, N = x.shape
-        FP = L.gwtf_padded_width(f)
-        ys = torch.zeros(_lib.STAT_REPLICAS, 2, FP, 2, device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            _lib.check(L.gwtf_train_stats(x.data_ptr(), pw.data_ptr(), ys.data_ptr(), B, N, f, pat, _lib.tune_word(), _lib._stream(x)))
-        ctx.save_for_backward(x, pw, pb)
-        ctx.meta = (pat, f, FP)
-        return ys.sum(0)[:, :f, :]
-
-    @staticmethod
-    def backward(ctx, gS):
-        x, pw, pb = ctx.saved_tensors
-        pat, f, FP = ctx.meta
-        L = _lib.lib()
-        B, _, N = x.shape
-        dev = x.device
-        gst = torch.zeros(2, 2, FP, device=dev, dtype=torch.float32)
-        gst[:, 0, :f] = gS[:, :, 0]
-        gst[:, 1, :f] = gS[:, :, 1]
-        g_x = torch.empty_like(x)
-        ws = _lib.dw1_workspace(f, B, N, dev)
-        g_sd0 = torch.zeros(_lib.STAT_REPLICAS, 2, 3, FP, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.check(L.gwtf_stats_backward(x.data_ptr(), gst.data_ptr(), pw.data_ptr(), pb.data_ptr(), g_x.data_ptr(),
-                                             ws.data_ptr(), g_sd0.data_ptr(), B, N, f, pat, _lib._stream(x)))
-        gW1 = _lib.dw1_reduce(ws, 1, f, B, N)
-        gs = g_sd0.sum(0)
-        return g_x, gs[:, 0:2, :f].permute(0, 2, 1).contiguous(), gs[:, 2, :f].contiguous(), gW1, None, None, None, None
-
-
-class ApplyFn(torch.autograd.Function):
-    """One coupling with given folded parameters: x -> (x_out, logvar, mu[detached])."""
-
-    @staticmethod
-    def forward(ctx, x, W0f, c0f, W1, cvec, u, b2, pw, pb, pat, f, eps, mode):
-        L = _lib.lib()
-        x = x.contiguous()
-        FP = L.gwtf_padded_width(f)
-        rec = film_record(cvec.unsqueeze(1), u.unsqueeze(1), b2.unsqueeze(0), FP)
-        out, lv, lists = _lib.stack_forward(x, pw, rec, 1, f, pat, eps, mode, True)
-        ctx.save_for_backward(x, pw, pb, rec)
-        ctx.meta = (pat, f, FP, eps, mode)
-        ctx.mark_non_differentiable(lists[1][0])
-        return out, lv, lists[1][0]
-
-    @staticmethod
-    def backward(ctx, g_out, g_lv, _g_mu):
-        x, pw, pb, rec = ctx.saved_tensors
-        pat, f, FP, eps, mode = ctx.meta
-        L = _lib.lib()
-        B, _, N = x.shape
-        dev = x.device
-        R = _lib.STAT_REPLICAS
-        g_out = (g_out if g_out is not None else torch.zeros_like(x)).contiguous()
-        g_lv = (g_lv if g_lv is not None else torch.zeros_like(x)).contiguous()
-        g_x = torch.empty_like(x)
-        g_film = torch.zeros(B, 1, 2, 3, FP, device=dev, dtype=torch.float32)
-        g_sd0 = torch.zeros(R, 2, 3, FP, device=dev, dtype=torch.float32)
-        g_bias = torch.zeros(R, 4, device=dev, dtype=torch.float32)
-        ws = _lib.dw1_workspace(f, B, N, dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.gwtf_coupling_backward(x.data_ptr(), g_out.data_ptr(), g_lv.data_ptr(), pw.data_ptr(), pb.data_ptr(),
-                                                rec.data_ptr(), g_x.data_ptr(), ws.data_ptr(),
-                                                g_film.data_ptr(), g_sd0.data_ptr(), g_bias.data_ptr(), 0, B, N, 1, f, pat,
-                                                float(eps), _lib._MODES[mode], _lib._stream(x)))
-        gW1 = _lib.dw1_reduce(ws, 1, f, B, N)
-        gs = g_sd0.sum(0)
-        return (g_x, gs[:, 0:2, :f].permute(0, 2, 1).contiguous(), gs[:, 2, :f].contiguous(), gW1,
-                g_film[:, 0, :, 0, :f].contiguous(), g_film[:, 0, :, 1:3, :f].contiguous(), g_bias.sum(0).reshape(2, 2),
-                None, None, None, None, None, None)
-
-
-class _BNSwishRows(torch.autograd.Function):
-    """hraw (B,C,2,2,f), BatchNorm weight / bias (C,2,2,f) (strided views of the raw arena) -> swish(BatchNorm over the B rows with
-    batch statistics), batch mean, biased batch variance: one HIP kernel per direction (csrc/gwtf_film.hip)."""
-
-    @staticmethod
-    def forward(ctx, hraw, hg, hb):
-        L = _lib.lib()
-        hraw = hraw.contiguous()
-        B, C, f = hraw.shape[0], hraw.shape[1], hraw.shape[-1]
-        M = hraw[0].numel()
-        if hg.stride() != hb.stride() or hg.stride(3) != 1 or hg.dtype != torch.float32:
-            hg, hb = hg.contiguous(), hb.contiguous()
-        y = torch.empty_like(hraw)
-        stats = torch.empty(3, M, device=hraw.device, dtype=torch.float32)
-        with torch.cuda.device(hraw.device):
-            _lib.check(L.gwtf_film_bn_swish_forward(hraw.data_ptr(), hg.data_ptr(), hb.data_ptr(), hg.stride(0), hg.stride(1),
-                                                    hg.stride(2), f, B, M, y.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
-                                                    stats[2].data_ptr(), _lib._stream(hraw)))
-        ctx.save_for_backward(hraw, hg, hb, stats)
-        mean, var = stats[0].view(hraw.shape[1:]), stats[1].view(hraw.shape[1:])
-        ctx.mark_non_differentiable(mean, var)
-        return y, mean, var
-
-    @staticmethod
-    def backward(ctx, gy, _gm, _gv):
-        hraw, hg, hb, stats = ctx.saved_tensors
-        L = _lib.lib()
-        B, f = hraw.shape[0], hraw.shape[-1]
-        M = hraw[0].numel()
-        gy = gy.contiguous()
-        gx = torch.empty_like(hraw)
-        gp = torch.empty(2, M, device=hraw.device, dtype=torch.float32)
-        with torch.cuda.device(hraw.device):
-            _lib.check(L.gwtf_film_bn_swish_backward(hraw.data_ptr(), gy.data_ptr(), hg.data_ptr(), hb.data_ptr(), hg.stride(0),
-                                                     hg.stride(1), hg.stride(2), f, B, M, stats[0].data_ptr(), stats[2].data_ptr(),
-                                                     gx.data_ptr(), gp[0].data_ptr(), gp[1].data_ptr(), _lib._stream(hraw)))
-        return gx, gp[0].view(hraw.shape[1:]), gp[1].view(hraw.shape[1:])
-
-
-PATHS = {'film_heads_hip': 0, 'film_heads_torch': 0}     # which FiLM-head implementation ran (tools/bench_train.py reports it)
-
-
-def _film_train(P, g, eps):
-    """FiLM heads with batch statistics over the B latent rows -> a, bsh (B,C,2,f) and batch {mean, unbiased var}.
-    torch ops: only the per-coupling cross-check chain (force_autograd_chain) comes through here."""
-    PATHS['film_heads_torch'] += 1
-    hg, hb, _, _ = P['hbn']
-    hraw = torch.einsum('bg,cxhfg->bcxhf', g, P['L0'])
-    Bn = hraw.shape[0]
-    hn, mean, var = _BNSwishRows.apply(hraw, hg, hb)
-    o = torch.einsum('bcxhi,cxhji->bcxhj', hn, P['L1']) + P['b1']
-    # + poison: a non-finite parameter anywhere in the branch makes the FiLM scale NaN, hence u = W2 a s1 and every output
-    # (the kernels' v_max ReLU alone would turn e.g. a NaN sd0 weight into a zero activation)
-    a = eps + torch.exp(o[:, :, :, 0]) + branch_poison(P['raw'], hraw.shape[1]).unsqueeze(0).unsqueeze(-1)
-    return a, o[:, :, :, 1], mean.detach(), (var * (Bn / max(Bn - 1.0, 1.0))).detach()
+PATHS = {'film_heads_hip': 0}     # which FiLM-head implementation ran (tools/bench_train.py reports it)
 
 
 class FilmHeadsFn(torch.autograd.Function):
@@ -469,116 +287,14 @@ class FilmHeadsFn(torch.autograd.Function):
         return (g_raw, dg_part.sum(0)) + (None,) * (ctx.n_in - 2)
 
 
-class _AllReduceSum(torch.autograd.Function):
-    """Sum over the ranks of the data-parallel group, in both directions: forward all-reduces the statistic,
-    backward all-reduces its gradient (every rank's loss depends on every rank's points through the batch
-    statistics -- SyncBatchNorm semantics, reference train_ae.py:152)."""
-
-    @staticmethod
-    def forward(ctx, t):
-        import torch.distributed as dist
-        from .dist import run
-        t = t.clone()
-        run(dist.all_reduce, t, op=dist.ReduceOp.SUM)
-        return t
-
-    @staticmethod
-    def backward(ctx, g):
-        import torch.distributed as dist
-        from .dist import run
-        g = g.clone().contiguous()
-        run(dist.all_reduce, g, op=dist.ReduceOp.SUM)
-        return g
-
-
-def train_density_forward(engine, p, g, distributed=False, mode='inverse'):
-    """Differentiable train-mode density pass.  Returns out, logdet, per-coupling lists (ps, mus, lvs in direct
-    order; ps/lvs differentiable) and bn_batch (C,2,4,2,f) for the running-statistic update.
-    distributed=True: statistics (and their gradients) are summed over torch.distributed's default group and the
-    per-shape FiLM BatchNorm sees the latents of all ranks."""
-    C, f, eps = engine.C, engine.f, engine.couplings[0]._eps_value
-    B, _, N = p.shape
-    P = _gather(engine)
-    group_sum = _AllReduceSum.apply if distributed else None
-    n = float(B * N)
-    g = g.float()
-    if distributed:
-        from .dist import gather_rows
-        g_all, lay = gather_rows(g)
-        row0, n = lay.row0, float(lay.total * N)
-        if g_all.shape[0] < 2:
-            raise ValueError('train-mode BatchNorm needs more than 1 shape per (global) batch')
-        a, bsh, fmean, fvar = _film_train(P, g_all, eps)
-        a, bsh = a[row0:row0 + B], bsh[row0:row0 + B]
-    else:
-        if B < 2:
-            raise ValueError('train-mode BatchNorm needs more than 1 shape per batch (torch raises the same)')
-        a, bsh, fmean, fvar = _film_train(P, g, eps)
-    bn_batch = torch.zeros(C, 2, 4, 2, f, device=p.device, dtype=torch.float32)
-    bn_batch[:, :, 2:4, 0] = fmean
-    bn_batch[:, :, 2:4, 1] = fvar
-    g0, be0, _, _ = P['bn0']
-    x = p.float().contiguous()
-    ps, mus, lvs = [None] * C, [None] * C, [None] * C
-    logdet = None
-    for c in (range(C - 1, -1, -1) if mode == 'inverse' else range(C)):
-        pat = (engine.pattern0 + c) % 6
-        k0, k1 = {0: (1, 2), 1: (0, 2), 2: (0, 1), 3: (2, -1), 4: (1, -1), 5: (0, -1)}[pat]
-        M = MomentsFn.apply(x)
-        if group_sum is not None:
-            M = group_sum(M)
-        # fold0: sd0_bn statistics are analytic in the moments of the kept coordinates (double: E[xx]-E[x]E[x] cancels)
-        Md = M.double()
-        E = Md[:3] / n
-        Sxx = torch.stack([torch.stack([Md[3], Md[4], Md[5]]), torch.stack([Md[4], Md[6], Md[7]]),
-                           torch.stack([Md[5], Md[7], Md[8]])]) / n
-        Cov = Sxx - torch.outer(E, E)
-        zero = Md.new_zeros(())            # python-int indexing only: no index tensors (hipGraph-capturable)
-        if k1 < 0:
-            Ek = torch.stack([E[k0], zero])
-            Ck = torch.stack([torch.stack([Cov[k0, k0], zero]), torch.stack([zero, zero])])
-        else:
-            Ek = torch.stack([E[k0], E[k1]])
-            Ck = torch.stack([torch.stack([Cov[k0, k0], Cov[k0, k1]]), torch.stack([Cov[k1, k0], Cov[k1, k1]])])
-        W0 = P['W0'][c].double()                                   # (2,f,2)
-        mean0 = W0 @ Ek
-        var0 = torch.einsum('xfa,ab,xfb->xf', W0, Ck, W0).clamp_min(0.0)
-        s0 = (g0[c].double() / torch.sqrt(var0 + BN_EPS))
-        W0f = (W0 * s0.unsqueeze(-1)).float()
-        c0f = (be0[c].double() - mean0 * s0).float()
-        W1 = P['W1'][c]
-        pw, pb = _pack_single(W1, W0f, c0f, f)
-        S = StatsFn.apply(x, W0f, c0f, W1, pw, pb, pat, f)
-        if group_sum is not None:
-            S = group_sum(S)
-        Sd = S.double()
-        m1 = Sd[..., 0] / n
-        v1 = (Sd[..., 1] / n - m1 * m1).clamp_min(0.0)
-        s1 = (1.0 / torch.sqrt(v1 + BN_EPS)).float()
-        as1 = a[:, c] * s1
-        cvec = -m1.float() + bsh[:, c] / as1
-        u = P['W2'][c].unsqueeze(0) * as1.unsqueeze(2)
-        x, lv, mu = ApplyFn.apply(x, W0f, c0f, W1, cvec, u, P['b2'][c], pw, pb, pat, f, eps, mode)
-        ps[c], mus[c], lvs[c] = x, mu, lv
-        logdet = lv if logdet is None else logdet + lv
-        with torch.no_grad():
-            unb = n / max(n - 1.0, 1.0)
-            bn_batch[c, :, 0, 0] = mean0.float()
-            bn_batch[c, :, 0, 1] = (var0 * unb).float()
-            bn_batch[c, :, 1, 0] = m1.float()
-            bn_batch[c, :, 1, 1] = (v1 * unb).float()
-    return x, logdet, (ps, mus, lvs), bn_batch
-
-
 # ======================================================================================================================
-# The train-mode density pass of K stacks at once through the K-batched, phase-split C pipeline (csrc/gwtf_train.hip,
-# include/gwtf.h GwtfTrainCtx): every kernel of the per-coupling chain above (folds and their backward included) takes all K
-# mixture components in one launch, and the chain is cut exactly where a data-parallel run sums BatchNorm statistics over
-# the ranks -- TWO collectives per depth level and direction for all K components and both branches (66 per forward of a
-# 33-coupling config; reference: SyncBatchNorm, train_ae.py:152, 8 layers x 33 couplings x K collectives).  A single rank
-# runs everything from two C calls.  Only the FiLM heads (O(B f G), vectorised over couplings) stay a torch graph.  The
-# chain of autograd nodes above remains as the cross-check (tests: test_train_fast_path_equals_autograd_chain and the
-# 2-rank test).
+# Train mode: batch-statistic BatchNorm (reference flows.py:27,30,62,65 under model.train(), with or without loss.backward()).
+# The statistics make every coupling depend on global reductions of its own input, so the pass of K stacks at once runs through
+# the K-batched, phase-split C pipeline (csrc/gwtf_train.hip, include/gwtf.h GwtfTrainCtx): per coupling fold0 -> stats ->
+# fold1 -> apply, every kernel (folds and their backward included) taking all K mixture components in one launch, and the chain
+# cut exactly where a data-parallel run sums BatchNorm statistics over the ranks -- TWO collectives per depth level and direction
+# for all K components and both branches (66 per forward of a 33-coupling config; reference: SyncBatchNorm, train_ae.py:152,
+# 8 layers x 33 couplings x K collectives).  A single rank runs everything from two C calls; the FiLM heads are FilmHeadsFn.
 # ======================================================================================================================
 COLLECTIVES = {'n': 0}        # statistic all-reduces issued by TrainMixtureFn (tests assert the count)
 GRAD_SINK = {'reducer': None}  # set by dist.OverlappedGradients: receives the decoders' flat gradient as soon as it exists
@@ -631,7 +347,7 @@ class TrainMixtureFn(torch.autograd.Function):
         shapes = dict(pb=(K * C * PB,), moments=(C + 1, K, R * 16), ystats=(C, K, R * 2 * FP * 2), bn_batch=(K, C, 2, 4, 2, f))
         zero = _zero_arena(shapes, dev)
         with torch.cuda.device(dev):
-            pw, _ = _lib.pack_weights(raw.view(-1), C, f, G, True, pattern0, K=K, stack_only=True)
+            pw, _ = _lib.pack_weights(raw.view(-1), C, f, G, True, pattern0, K=K)
             pb = zero['pb']
             _lib.check(L.gwtf_pack_w1t(raw.data_ptr(), pb.data_ptr(), K * C, f, G, _lib._stream(p)))
         t = _lib.TrainCtx()
@@ -792,7 +508,8 @@ def train_density_forward_multi(engines, p, g, mode='inverse', distributed=False
     return out, logdet, lists, bn_batch
 
 
-def train_density_forward_fast(engine, p, g, mode='inverse', distributed=False):
-    """One stack through the fused pipeline.  -> out, logdet (B,3,N), lists = (ps, mus, lvs) (C,B,3,N) each, bn_batch (C,2,4,2,f)."""
-    out, logdet, lists, bn_batch = train_density_forward_multi([engine], p, g, mode, distributed)
-    return out[0], logdet[0], tuple(t[0] for t in lists), bn_batch[0]
+def train_density_forward_fast(engine, p, g, mode='inverse', distributed=False, want_lists=True):
+    """One stack through the fused pipeline.  -> out, logdet (B,3,N), lists = (ps, mus, lvs) (C,B,3,N) each (None unless
+    want_lists), bn_batch (C,2,4,2,f)."""
+    out, logdet, lists, bn_batch = train_density_forward_multi([engine], p, g, mode, distributed, want_lists)
+    return out[0], logdet[0], tuple(t[0] for t in lists) if want_lists else None, bn_batch[0]

@@ -48,11 +48,7 @@ struct BCfg {
 };
 
 // VAR selects what one pass over the points does:
-//   BW_DIRECT  backward of the coupling itself (BatchNorm as a fixed affine map: the eval-mode backward, and the first half of
-//              the two-pass train-mode chain of the per-coupling autograd nodes).
-//   BW_STATS   backward of the train-mode statistics pass (gwtf_train_stats): the upstream is g_stats[branch][{d/dSum y,
-//              d/dSum y^2}][FP], i.e. dL/dy(p) = gS + 2 gQ y(p) for every point, y = un-biased accumulator (no FiLM record, no
-//              tail); everything after dacc is shared.
+//   BW_DIRECT  backward of the coupling itself (BatchNorm as a fixed affine map: the eval-mode backward).
 //   BW_LIGHT / BW_MERGED   the train pipeline's two passes.  g_stats depends on the coupling path only through the per-shape sums of
 //              dacc and dacc-weighted activations (the FiLM-record gradients, fold1_bwd_kernel), so LIGHT recomputes the forward and
 //              the tail's backward and leaves ONLY those sums (and the sd2 bias sums); MERGED then runs the expensive part -- dh = W1^T
@@ -63,7 +59,7 @@ struct BCfg {
 // 0: one kept / two warped; -1: read from `pat`).  With one warped coordinate the second output column of sd2 does not exist: its
 // u_1 terms, its FiLM-record sum (one of three 16-lane reductions + LDS atomics per feature row in the light pass) and the second
 // tail slot fold away -- the train pipeline's launcher picks the variant per level (the pattern is a host-side fact).
-enum { BW_DIRECT = 0, BW_STATS = 1, BW_LIGHT = 2, BW_MERGED = 3 };
+enum { BW_DIRECT = 0, BW_LIGHT = 2, BW_MERGED = 3 };
 // FULL: N is a multiple of the workgroup's tile (no point beyond the cloud: the per-element bound selects of the merged pass fold away).
 template <int MB, int NB, int VAR, int MG = -1, int K2 = -1, bool FULL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2 : (MB <= 3 ? 3 : 1)))) void bwd_kernel(const float* __restrict__ x_in, const float* __restrict__ g_out,
@@ -79,7 +75,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
   using K = Cfg<MB>;
   using KB = BCfg<MB>;
   constexpr int FP = K::FP;
-  constexpr bool STATS = VAR == BW_STATS, LIGHT = VAR == BW_LIGHT, MERGED = VAR == BW_MERGED;
+  constexpr bool LIGHT = VAR == BW_LIGHT, MERGED = VAR == BW_MERGED;
   {
     // blockIdx.y = mixture component of the K-batched train pipeline (all strides 0, Ctot == C for a single stack)
     const size_t comp = blockIdx.y;
@@ -90,26 +86,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
     dw1_ws += comp * ks_.dw1;
     g_sd0 += comp * ks_.gsd0;
     if (MERGED) g_stats += comp * ks_.gstats;
-    if (!STATS) {
-      g_out += comp * ks_.pts;
-      g_ld += comp * ks_.pts;
-      // gradients entering through this coupling's own list slots (ps[c], logvars[c]; lists are [K][Cper][B][3][N])
-      if (g_ps_c) g_ps_c += comp * ks_.Cper * ks_.pts;
-      if (g_lvs_c) g_lvs_c += comp * ks_.Cper * ks_.pts;
-      g_bias += comp * ks_.gbias;
-      c += (int)comp * ks_.Cper;     // FiLM-side arrays: [shape][Ctot][...], coupling k*Cper + c
-      C = ks_.Ctot;
-    } else {
-      g_stats += comp * ks_.gstats;
-    }
+    g_out += comp * ks_.pts;
+    g_ld += comp * ks_.pts;
+    // gradients entering through this coupling's own list slots (ps[c], logvars[c]; lists are [K][Cper][B][3][N])
+    if (g_ps_c) g_ps_c += comp * ks_.Cper * ks_.pts;
+    if (g_lvs_c) g_lvs_c += comp * ks_.Cper * ks_.pts;
+    g_bias += comp * ks_.gbias;
+    c += (int)comp * ks_.Cper;     // FiLM-side arrays: [shape][Ctot][...], coupling k*Cper + c
+    C = ks_.Ctot;
   }
   __shared__ __align__(16) float lds[K::PW + K::FSP + (LIGHT ? 0 : KB::PB_LDS)];
   // sd0 sums: one set per workgroup (atomics), or one per wave (GWTF_ROWSUM_KEEP >= 2: plain stores, summed by the flush)
   constexpr int SD0W = (GWTF_ROWSUM_KEEP >= 2 && GWTF_ROWSUM_MODE == 1 && !LIGHT) ? 4 : 1;
   __shared__ float s_film[2][3][FP], s_sd0[SD0W][2][3][FP], s_bias[4];
-  // MERGED / STATS: the statistics' upstream g_stats [2][2][FP] staged once per workgroup (read from global memory where it is used
+  // MERGED: the statistics' upstream g_stats [2][2][FP] staged once per workgroup (read from global memory where it is used
   // it was 48 conditional loads -- each its own exec-masked block -- per wave inside the dacc loop)
-  __shared__ __align__(16) float s_gst[(STATS || MERGED) ? 4 * FP : 4];
+  __shared__ __align__(16) float s_gst[MERGED ? 4 * FP : 4];
   // dW1 machinery: coordinates of the workgroup's points, per-wave |dacc| maxima, the transposed dacc image
   constexpr int PTS = 64 * NB;                      // points per workgroup
   constexpr int XPITCH = 2 * PTS + 8;               // bytes per feature row (+8: rows land 8 B apart in the banks)
@@ -125,7 +117,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
   for (int t = threadIdx.x; t < 2 * 3 * FP; t += blockDim.x) (&s_film[0][0][0])[t] = 0.f;
   for (int t = threadIdx.x; t < SD0W * 2 * 3 * FP; t += blockDim.x) (&s_sd0[0][0][0][0])[t] = 0.f;
   if (threadIdx.x < 4) s_bias[threadIdx.x] = 0.f;
-  if (STATS || MERGED)
+  if (MERGED)
     for (int t = threadIdx.x; t < 4 * FP; t += blockDim.x) s_gst[t] = (t % FP) < f ? g_stats[t] : 0.f;
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -149,7 +141,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
       if (piece < K::PW / 256)
         __builtin_amdgcn_global_load_lds((glb_void*)(pw_c + piece * 256 + lane * 4), (lds_void*)&lds[piece * 256], 16, 0, 0);
     }
-    if (!STATS && wave < K::FSP / 256 && wave * 256 + lane * 4 < K::FS)
+    if (wave < K::FSP / 256 && wave * 256 + lane * 4 < K::FS)
       __builtin_amdgcn_global_load_lds((glb_void*)(src_f + wave * 256), (lds_void*)&lds[K::PW + wave * 256], 16, 0, 0);
     for (int piece = wave; !LIGHT && piece * 256 < KB::W1T; piece += 4)        // W1T of branch 0 (W1T is a multiple of 256 floats)
       __builtin_amdgcn_global_load_lds((glb_void*)(pb_c + piece * 256 + lane * 4),
@@ -195,10 +187,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
   for (int d = 0; d < 3; ++d) {
     const size_t o = ((size_t)b * 3 + d) * N + n_own;
     xo[d] = own_inrange ? x_in[o] : 0.f;
-    go[d] = (!STATS && own_inrange) ? g_out[o] : 0.f;
-    gl[d] = (!STATS && own_inrange) ? g_ld[o] : 0.f;
-    if (!STATS && own_inrange && g_ps_c) go[d] += g_ps_c[o];
-    if (!STATS && own_inrange && g_lvs_c) gl[d] += g_lvs_c[o];
+    go[d] = own_inrange ? g_out[o] : 0.f;
+    gl[d] = own_inrange ? g_ld[o] : 0.f;
+    if (own_inrange && g_ps_c) go[d] += g_ps_c[o];
+    if (own_inrange && g_lvs_c) gl[d] += g_lvs_c[o];
   }
   float xa[NB], xb[NB];
 #pragma unroll
@@ -220,14 +212,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
     const float* fe = L + K::PW + br * 3 * FP + 4 * q;
     f32x4 cinit[MB];
 #pragma unroll
-    for (int m = 0; m < MB; ++m) cinit[m] = STATS ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(fe + 16 * m);
+    for (int m = 0; m < MB; ++m) cinit[m] = *reinterpret_cast<const f32x4*>(fe + 16 * m);
     // The dispatch stays a RUN-TIME branch on `pat` even where K2 fixes the pattern at compile time: with a constant condition the
     // contraction (its f16 splits are inline asm) is inlined into the surrounding basic block and the merged pass came out wrong
     // (errors of 1e-4 .. O(1) in dL/dx at 128 x 2048, f = 37; the asm-hazard rule of docs/LOG.md: a value produced by inline asm is
     // consumed in the block that produces it).
     if (pat < 3) sd1_contract<MB, NB, true, MG>(L, br, kk_steps, lane, q, xa, xb, cinit, acc[br]);
     else sd1_contract<MB, NB, false, MG>(L, br, kk_steps, lane, q, xa, xb, cinit, acc[br]);
-    if (STATS) continue;
     float o0[NB], o1[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) o0[nb] = o1[nb] = 0.f;
@@ -247,7 +238,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
     res[br][0] = quarter_reduce<NB>(o0, q);
     if (!ONE_W) res[br][1] = quarter_reduce<NB>(o1, q);
   }
-  const f32x4 bias = STATS ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(L + K::PW + 6 * FP);
+  const f32x4 bias = *reinterpret_cast<const f32x4*>(L + K::PW + 6 * FP);
   const float s_keep = sqrtf(eps + 1.0f);
 
   // ---- tail forward + backward on the own point ------------------------------------------------------------
@@ -263,7 +254,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
   float t_rden[2] = {0.f, 0.f}, t_e[2] = {0.f, 0.f}, t_sc[2] = {1.f, 1.f}, t_rsc[2] = {1.f, 1.f}, t_out[2] = {0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    if (!STATS && s < nw) {
+    if (s < nw) {
       const float t = res[0][s] + bias[s];
       const float den = 1.0f + fabsf(t);
       t_rden[s] = __builtin_amdgcn_rcpf(den);
@@ -295,7 +286,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
   }
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    if (!STATS && s < nw) {
+    if (s < nw) {
       float dsc;
       if (mode == GWTF_MODE_INVERSE) {       // out = (x - mu)/s
         gx[s] = gow[s] * t_rsc[s];
@@ -312,8 +303,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
   }
   float gin[3];
 #pragma unroll
-  for (int d = 0; d < 3; ++d) gin[d] = STATS ? 0.f : (d == w0 ? gx[0] : ((!keep2 && d == w1) ? gx[1] : go[d] * keep_scale));
-  if (!STATS && !MERGED) {  // sd2 bias gradient: sum of dt over the wave's valid points
+  for (int d = 0; d < 3; ++d) gin[d] = d == w0 ? gx[0] : ((!keep2 && d == w1) ? gx[1] : go[d] * keep_scale);
+  if (!MERGED) {  // sd2 bias gradient: sum of dt over the wave's valid points
     float bsum[4] = {own_valid ? dt[0][0] : 0.f, own_valid ? dt[0][1] : 0.f, own_valid ? dt[1][0] : 0.f,
                      own_valid ? dt[1][1] : 0.f};
 #pragma unroll
@@ -341,22 +332,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
     const float* fe = L + K::PW + br * 3 * FP + 4 * q;
 #pragma unroll
     for (int m = 0; m < MB; ++m) {
-      const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-      const f32x4 u0 = STATS ? zero4 : *reinterpret_cast<const f32x4*>(fe + FP + 16 * m);
-      const f32x4 u1 = STATS ? zero4 : *reinterpret_cast<const f32x4*>(fe + 2 * FP + 16 * m);
+      const f32x4 u0 = *reinterpret_cast<const f32x4*>(fe + FP + 16 * m);
+      const f32x4 u1 = *reinterpret_cast<const f32x4*>(fe + 2 * FP + 16 * m);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int ft = 16 * m + 4 * q + r;
-        if (STATS) {
-          const float gs = s_gst[(br * 2 + 0) * FP + ft], gq2 = 2.0f * s_gst[(br * 2 + 1) * FP + ft];
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb) {
-            const int n = n_wave0 + 16 * nb + i16;
-            const float da = n < N ? fmaf(gq2, acc[br][m][nb][r], gs) : 0.f;
-            acc[br][m][nb][r] = da;
-          }
-          continue;
-        }
         if (MERGED) {     // dy = dacc (coupling path) + gS + 2 gQ y (statistics path), y = acc - c; the FiLM sums were LIGHT's job
           const float gs = s_gst[(br * 2 + 0) * FP + ft], gq2 = 2.0f * s_gst[(br * 2 + 1) * FP + ft];
           const float cc = fe[16 * m + r];
@@ -580,7 +560,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
   float* gf = g_film + ((size_t)b * C + c) * (2 * 3 * FP);
   float* gs = g_sd0 + (size_t)(blockIdx.x % GWTF_STAT_REPLICAS) * (2 * 3 * FP);
   for (int t = threadIdx.x; t < 2 * 3 * FP; t += blockDim.x) {
-    if (!STATS && !MERGED) atomicAdd(&gf[t], (&s_film[0][0][0])[t]);
+    if (!MERGED) atomicAdd(&gf[t], (&s_film[0][0][0])[t]);
     if (!LIGHT) {
       float v = (&s_sd0[0][0][0][0])[t];
 #pragma unroll
@@ -588,7 +568,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2
       atomicAdd(&gs[t], v);
     }
   }
-  if (!STATS && !MERGED && threadIdx.x < 4) atomicAdd(&g_bias[(blockIdx.x % GWTF_STAT_REPLICAS) * 4 + threadIdx.x], s_bias[threadIdx.x]);
+  if (!MERGED && threadIdx.x < 4) atomicAdd(&g_bias[(blockIdx.x % GWTF_STAT_REPLICAS) * 4 + threadIdx.x], s_bias[threadIdx.x]);
 }
 
 // folded parameters (what autograd differentiates) -> forward + backward packed records, see gwtf_layout.h
@@ -733,12 +713,6 @@ extern "C" int gwtf_pack_folded(const float* W1p, const float* W0f, const float*
   return (int)hipGetLastError();
 }
 
-extern "C" int gwtf_coupling_backward_lists(const float* x_in, const float* g_out, const float* g_ld, const float* g_ps_c,
-                                            const float* g_lvs_c, const float* packed_w_c, const float* packed_b_c,
-                                            const float* film, float* g_in, float* dw1_ws, float* g_film, float* g_sd0,
-                                            float* g_bias, int c, int B, int N, int C, int f, int pattern0, float eps, int mode,
-                                            void* stream);
-
 static int bwd_points_per_wg(int B, int N) { return (long)B * N >= 2048L * 32 ? 128 : 64; }
 static int bwd_grid(int B, int N) {
   const int pts = bwd_points_per_wg(B, N);
@@ -756,7 +730,6 @@ static int bwd_dispatch(int var, const float* x_in, const float* g_out, const fl
 #define GWTF_V(MB_)                                                                                     \
   switch (var) {                                                                                        \
     case BW_DIRECT: return launch_bwd<MB_, BW_DIRECT>(nb, GWTF_A);                                      \
-    case BW_STATS: return launch_bwd<MB_, BW_STATS>(nb, GWTF_A);                                        \
     case BW_LIGHT: return launch_bwd<MB_, BW_LIGHT>(nb, GWTF_A);                                        \
     default: return launch_bwd<MB_, BW_MERGED>(nb, GWTF_A);                                             \
   }
@@ -771,14 +744,6 @@ static int bwd_dispatch(int var, const float* x_in, const float* g_out, const fl
   }
 #undef GWTF_A
 #undef GWTF_V
-}
-
-extern "C" int gwtf_coupling_backward(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
-                                      const float* packed_b_c, const float* film, float* g_in, float* dw1_ws, float* g_film,
-                                      float* g_sd0, float* g_bias, int c, int B, int N, int C, int f, int pattern0, float eps,
-                                      int mode, void* stream) {
-  return gwtf_coupling_backward_lists(x_in, g_out, g_ld, nullptr, nullptr, packed_w_c, packed_b_c, film, g_in, dw1_ws, g_film,
-                                      g_sd0, g_bias, c, B, N, C, f, pattern0, eps, mode, stream);
 }
 
 extern "C" int gwtf_coupling_backward_lists(const float* x_in, const float* g_out, const float* g_ld, const float* g_ps_c,
@@ -796,16 +761,9 @@ extern "C" int gwtf_coupling_backward_lists(const float* x_in, const float* g_ou
                       B, N, C, f, (pattern0 + c) % 6, eps, mode, 1, ks, g_ps_c, g_lvs_c, GwtfCombine{}, stream);
 }
 
-// K-batched variants (train pipeline, gwtf_train.hip): component k adds k * stride (GwtfKS) to every base pointer
-int gwtf_internal_coupling_backward_k(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
-                                      const float* packed_b_c, const float* film, float* g_in, float* dw1_ws, float* g_film,
-                                      float* g_sd0, float* g_bias, int c, int K, int B, int N, int f, int pattern0, float eps,
-                                      int mode, const GwtfKS& ks, const float* g_ps_c, const float* g_lvs_c, void* stream) {
-  return bwd_dispatch(BW_DIRECT, x_in, g_out, g_ld, packed_w_c, packed_b_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, nullptr, c,
-                      B, N, ks.Ctot, f, (pattern0 + c) % 6, eps, mode, K, ks, g_ps_c, g_lvs_c, GwtfCombine{}, stream);
-}
-// The train pipeline's two passes (BW_LIGHT / BW_MERGED above).  light: only g_film and g_bias are written; merged: g_in, the dW1
-// partials and g_sd0, with the statistics path's upstream g_stats [K][2][2][FP] added to dacc.
+// The train pipeline's two passes (BW_LIGHT / BW_MERGED above; gwtf_train.hip): component k adds k * stride (GwtfKS) to every base
+// pointer.  light: only g_film and g_bias are written; merged: g_in, the dW1 partials and g_sd0, with the statistics path's upstream
+// g_stats [K][2][2][FP] added to dacc.
 int gwtf_internal_light_backward_k(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
                                    const float* film, float* g_film, float* g_bias, int c, int K, int B, int N, int f,
                                    int pattern0, float eps, int mode, const GwtfKS& ks, const float* g_ps_c,
@@ -822,24 +780,6 @@ int gwtf_internal_merged_backward_k(const float* x_in, const float* g_out, const
   return bwd_dispatch(BW_MERGED, x_in, g_out, g_ld, packed_w_c, packed_b_c, film, g_in, dw1_ws, g_sd0 /*unused*/, g_sd0,
                       g_sd0 /*unused*/, g_stats, c, B, N, ks.Ctot, f, (pattern0 + c) % 6, eps, mode, K, ks, g_ps_c, g_lvs_c, cmb,
                       stream);
-}
-int gwtf_internal_stats_backward_k(const float* x_in, const float* g_stats, const float* packed_w_c, const float* packed_b_c,
-                                   float* g_in, float* dw1_ws, float* g_sd0, int K, int B, int N, int f, int pattern,
-                                   const GwtfKS& ks, void* stream) {
-  return bwd_dispatch(BW_STATS, x_in, nullptr, nullptr, packed_w_c, packed_b_c, packed_w_c /*unused*/, g_in, dw1_ws,
-                      g_sd0 /*unused*/, g_sd0, g_sd0 /*unused*/, g_stats, 0, B, N, 1, f, pattern, 0.f, GWTF_MODE_INVERSE, K, ks,
-                      nullptr, nullptr, GwtfCombine{}, stream);
-}
-
-extern "C" int gwtf_stats_backward(const float* x_in, const float* g_stats, const float* packed_w_c,
-                                   const float* packed_b_c, float* g_in, float* dw1_ws, float* g_sd0, int B, int N, int f,
-                                   int pattern, void* stream) {
-  if (!x_in || !g_stats || !packed_w_c || !packed_b_c || !g_in || !dw1_ws || !g_sd0 || B <= 0 || N <= 0 || f <= 0 ||
-      f > GWTF_MAX_FP_TRAIN || pattern < 0 || pattern > 5)
-    return GWTF_E_BADARG;
-  GwtfKS ks = {};
-  ks.Cper = ks.Ctot = 1;
-  return gwtf_internal_stats_backward_k(x_in, g_stats, packed_w_c, packed_b_c, g_in, dw1_ws, g_sd0, 1, B, N, f, pattern, ks, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

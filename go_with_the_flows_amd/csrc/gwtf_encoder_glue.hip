@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void enc_mform_kernel(const float* __restrict_
 }
 
 // M 2^k (k = 8 - floor(log2 max|M|): the operand scale that keeps the f16 split of M in range) -> hi/lo fragment images in the unit
-// order of enc_train_pack_kernel (gwtf_encoder_train.hip:69); block 0 also writes mconst[C3..C3+4) = {2^-k, 0, 0, 0}
+// order of enc_train_pack_all_kernel (gwtf_encoder_train.hip:66); block 0 also writes mconst[C3..C3+4) = {2^-k, 0, 0, 0}
 __global__ __launch_bounds__(256) void enc_mform_pack_kernel(const float* __restrict__ M, const float* __restrict__ tmax, int n_tiles,
                                                              float* __restrict__ units, float* __restrict__ mconst, int C3) {
   __shared__ float red[4];

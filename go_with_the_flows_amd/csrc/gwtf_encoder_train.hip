@@ -65,26 +65,8 @@ __device__ __forceinline__ size_t tix(int b, int C, int ch, int n, int N) {
 
 // units [m][ks] of [hi | lo] x 64 lanes x 8 f16: A-operand row 16 m + (lane & 15), k-slot (ks, q, e) <-> contraction index
 // 32 ks + 16 (e >> 2) + 4 q + (e & 3) (the map gwtf_encoder.hip uses).  transposed = 0: A[row][k] = W[row][k] (W [rows][kdim]);
-// transposed = 1: A[row][k] = W[k][row] (W [kdim][rows]).
-__global__ void enc_train_pack_kernel(const float* __restrict__ W, float* __restrict__ units, int rows, int kdim, int transposed) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int KS = kdim / 32;
-  if (t >= (rows / 16) * KS * 2 * 64) return;
-  const int lane = t & 63, part = (t >> 6) & 1, unit = t >> 7;
-  const int m = unit / KS, ks = unit % KS;
-  const int row = 16 * m + (lane & 15), q = lane >> 4;
-  _Float16 out[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int k = 32 * ks + 16 * (e >> 2) + 4 * q + (e & 3);
-    const float v = transposed ? W[(size_t)k * rows + row] : W[(size_t)row * kdim + k];
-    const _Float16 hi = (_Float16)v;
-    out[e] = part == 0 ? hi : (_Float16)(v - (float)hi);
-  }
-  *reinterpret_cast<float4*>(units + (size_t)unit * 512 + part * 256 + lane * 4) = *reinterpret_cast<const float4*>(out);
-}
-
-// the six fragment images of layers 1..3 (forward + transposed) in ONE launch: blockIdx.y = job
+// transposed = 1: A[row][k] = W[k][row] (W [kdim][rows]).  The six fragment images of layers 1..3 (forward + transposed) in ONE
+// launch: blockIdx.y = job
 struct PackJobs { const float* W[6]; float* units[6]; int rows[6], kdim[6], transposed[6]; };
 __global__ void enc_train_pack_all_kernel(const PackJobs J) {
   const int j = blockIdx.y;
@@ -1202,17 +1184,7 @@ extern "C" size_t gwtf_enc_train_units_floats(int layer) {
   return (size_t)(kC[layer + 1] / 16) * (kC[layer] / 32) * 512;
 }
 
-extern "C" int gwtf_enc_train_pack(const float* W, float* units_fwd, float* units_bwd, int layer, void* stream) {
-  if (!W || !units_fwd || !units_bwd || layer < 1 || layer > 3) return GWTF_E_BADARG;
-  const int cin = kC[layer], cout = kC[layer + 1];
-  const int total = (cout / 16) * (cin / 32) * 2 * 64;     // == (cin / 16) * (cout / 32) * 2 * 64
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(enc_train_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, W, units_fwd, cout, cin, 0);
-  hipLaunchKernelGGL(enc_train_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, W, units_bwd, cin, cout, 1);
-  return (int)hipGetLastError();
-}
-
-// all three layers' images from one launch (what the training step calls: six launches of gwtf_enc_train_pack otherwise)
+// all three layers' images from one launch
 extern "C" int gwtf_enc_train_pack_all(const float* W1, const float* W2, const float* W3, float* uf1, float* ub1, float* uf2, float* ub2,
                                        float* uf3, float* ub3, void* stream) {
   if (!W1 || !W2 || !W3 || !uf1 || !ub1 || !uf2 || !ub2 || !uf3 || !ub3) return GWTF_E_BADARG;
@@ -1226,14 +1198,6 @@ extern "C" int gwtf_enc_train_pack_all(const float* W1, const float* W2, const f
     J.W[2 * l - 1] = Ws[l - 1]; J.units[2 * l - 1] = ub[l - 1]; J.rows[2 * l - 1] = cin; J.kdim[2 * l - 1] = cout; J.transposed[2 * l - 1] = 1;
   }
   hipLaunchKernelGGL(enc_train_pack_all_kernel, dim3(64, 6), dim3(256), 0, (hipStream_t)stream, J);
-  return (int)hipGetLastError();
-}
-
-// a (rows x kdim) row-major matrix -> fragment images (rows % 16 == 0, kdim % 32 == 0): the top layer's M = W_3^T diag(Q) W_3
-extern "C" int gwtf_enc_train_pack_matrix(const float* W, float* units, int rows, int kdim, void* stream) {
-  if (!W || !units || rows <= 0 || kdim <= 0 || rows % 16 || kdim % 32) return GWTF_E_BADARG;
-  const int total = (rows / 16) * (kdim / 32) * 2 * 64;
-  hipLaunchKernelGGL(enc_train_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, W, units, rows, kdim, 0);
   return (int)hipGetLastError();
 }
 

@@ -37,7 +37,7 @@ __device__ inline void abs_columns(const float* rb, const GwtfRaw& R, int f, int
 // Range scaling exponents + poison of every (coupling, branch) -> packed_film's RS / CS / POISON slots (gwtf_layout.h).
 // One workgroup per branch record; runs before the two gather kernels below, which read the exponents.
 __global__ __launch_bounds__(256) void pack_scales_kernel(const float* __restrict__ raw, float* __restrict__ pf, int C, int f,
-                                                          int G, int FP, int training, int pattern0, int Cper) {
+                                                          int G, int FP, int pattern0, int Cper) {
   const GwtfRaw R(f, G);
   const GwtfPackF P(FP, G);
   const int cb = blockIdx.x, c = cb >> 1, t = threadIdx.x;
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void pack_scales_kernel(const float* __restric
   if (bad) s_bad = 1;
   if (t < FP) {
     int cs = 0;
-    if (!training && t < f) {
+    if (t < f) {
       const float* bn = rb + R.bn0();
       const float s = bn[t] * inv_std(bn[3 * f + t]);
       const int k = gwtf_pattern_kept((pattern0 + c % Cper) % 6);
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void pack_scales_kernel(const float* __restric
   __syncthreads();
   if (t < FP) {
     int rs = 0;
-    if (!training && t < f) {
+    if (t < f) {
       const float sc = inv_std(rb[R.bn1() + f + t]);
       float m = 0.f;
       for (int j = 0; j < f; ++j) m = fmaxf(m, fabsf(ldexpf(rb[R.sd1_w() + (size_t)t * f + j] * sc, s_cs[j])));
@@ -123,7 +123,7 @@ __global__ void pack_w_kernel(const float* __restrict__ raw, const float* __rest
           const float hi = __half2float(__float2half_rn(w));
           e[t] = sl.lo ? (w - hi) : hi;
         }
-        if (absf && sl.zero && !training) {    // train packing: gwtf_train_fold0 writes the columns per level (batch statistics)
+        if (absf && sl.zero && !training) {    // train packing: the pipeline's fold0 writes the columns per level (batch statistics)
           double Ca, Cb, Cc;
           abs_columns(rb, R, f, jo, gwtf_pattern_kept((pattern0 + c % Cper) % 6), sc, &Ca, &Cb, &Cc);
           gwtf_abs_cols(lane >> 4, (float)ldexp(Ca, -rs - 1), (float)ldexp(Cb, -rs - 1), (float)ldexp(Cc, -rs - 1), &e[0], &e[1]);
@@ -137,7 +137,7 @@ __global__ void pack_w_kernel(const float* __restrict__ raw, const float* __rest
       const float* rb = raw + (size_t)c * R.coupling_size() + (size_t)br * R.branch_size();
       const int j = (int)(o % 8), e = (int)((o / 8) % 3), q = (int)((o / 24) % 4), ks = (int)(o / 96);
       const int ft = 32 * ks + 4 * j + q;
-      if (ft < f && !training) {   // train: written per coupling by gwtf_train_fold0
+      if (ft < f && !training) {   // train: written per coupling by the pipeline's fold0
         const float* bn = rb + R.bn0();
         const float s = bn[ft] * inv_std(bn[3 * f + ft]);
         const int k = gwtf_pattern_kept((pattern0 + c % Cper) % 6);
@@ -150,8 +150,7 @@ __global__ void pack_w_kernel(const float* __restrict__ raw, const float* __rest
 }
 
 // packed FiLM weights
-__global__ void pack_film_kernel(const float* __restrict__ raw, float* __restrict__ out, int C, int f, int G, int FP,
-                                 int training) {
+__global__ void pack_film_kernel(const float* __restrict__ raw, float* __restrict__ out, int C, int f, int G, int FP) {
   const GwtfRaw R(f, G);
   const GwtfPackF P(FP, G);
   const size_t perb = P.branch_size();
@@ -160,32 +159,24 @@ __global__ void pack_film_kernel(const float* __restrict__ raw, float* __restric
     const int cb = (int)(idx / perb);  // coupling*2 + branch
     size_t o = idx - (size_t)cb * perb;
     const float* rb = raw + (size_t)cb * R.branch_size();  // coupling_size == 2*branch_size
-    const float* rsx = out + (size_t)cb * perb + P.rs();   // row exponents, written by pack_scales_kernel (zeros in train packing)
+    const float* rsx = out + (size_t)cb * perb + P.rs();   // row exponents, written by pack_scales_kernel
     float v = 0.f;
     if (o >= P.poison()) continue;                         // POISON, RS, CS: pack_scales_kernel's
     if (o < P.c1()) {
       const int which = (int)(o / P.mlp_size());
       o -= (size_t)which * P.mlp_size();
       const float* bn = rb + R.film_bn(which);
-      if (o < (size_t)P.GP() * FP) {  // L0T[i][j] = L0[j][i], rows G..GP-1 zero; eval: four latent columns interleaved
-        int i = (int)(o / FP), j = (int)(o % FP);
-        if (!training) {               // L0Q[i/4][j][i%4]: the eval kernel's lane (feature j) reads 4 k-slots with one dwordx4
-          i = 4 * (int)(o / (4 * (size_t)FP)) + (int)(o % 4);
-          j = (int)((o / 4) % FP);
-        }
+      if (o < (size_t)P.GP() * FP) {  // L0Q[i/4][j][i%4] = L0[j][i], rows G..GP-1 zero: the kernel's lane (feature j) reads 4 k-slots with one dwordx4
+        const int i = 4 * (int)(o / (4 * (size_t)FP)) + (int)(o % 4), j = (int)((o / 4) % FP);
         if (j < f && i < G) v = rb[R.film_l0(which) + (size_t)j * G + i];
       } else if ((o -= (size_t)P.GP() * FP) < (size_t)FP) {  // S
         const int j = (int)o;
-        if (j < f) v = training ? bn[j] : bn[j] * inv_std(bn[3 * f + j]);
+        if (j < f) v = bn[j] * inv_std(bn[3 * f + j]);
       } else if ((o -= FP) < (size_t)FP) {  // T
         const int j = (int)o;
-        if (j < f) v = training ? bn[f + j] : bn[f + j] - bn[2 * f + j] * (bn[j] * inv_std(bn[3 * f + j]));
-      } else if ((o -= FP) < (size_t)FP * FP) {  // L1T[i][j] = L1[j][i]; eval: L1Q[i/4][j][i%4] like L0Q
-        int i = (int)(o / FP), j = (int)(o % FP);
-        if (!training) {
-          i = 4 * (int)(o / (4 * (size_t)FP)) + (int)(o % 4);
-          j = (int)((o / 4) % FP);
-        }
+        if (j < f) v = bn[f + j] - bn[2 * f + j] * (bn[j] * inv_std(bn[3 * f + j]));
+      } else if ((o -= FP) < (size_t)FP * FP) {  // L1Q[i/4][j][i%4] = L1[j][i], like L0Q
+        const int i = 4 * (int)(o / (4 * (size_t)FP)) + (int)(o % 4), j = (int)((o / 4) % FP);
         if (i < f && j < f) v = rb[R.film_l1(which) + (size_t)j * f + i];
         if (which == 1 && j < f) v = ldexpf(v, -(int)rsx[j]);   // the b head produces b 2^-RS: c = C1' + b'/a = 2^-RS (c1 + b/a)
       } else {  // L1B
@@ -265,27 +256,26 @@ extern "C" int gwtf_pack_weights_exact(const float* raw, const float* packed_fil
 extern "C" int gwtf_pack_weights_k(const float* raw, float* packed_w, float* packed_film, int K, int Cper, int f, int G,
                                    int pattern0, int training, void* stream) {
   const int C = K * Cper;
-  // training == 2: the train pipeline's packing -- the stack weights only (its FiLM heads read the raw arena in place,
+  // training = 1: the train pipeline's packing -- the stack weights only (its FiLM heads read the raw arena in place,
   // csrc/gwtf_film_train.hip; no range-scaling exponents in train mode): packed_film may be NULL
-  const bool stack_only = training == 2;
-  if (K <= 0 || Cper <= 0 || f <= 0 || G <= 0 || f > GWTF_MAX_FP || !raw || !packed_w || (!packed_film && !stack_only) || pattern0 < 0 ||
-      pattern0 > 5)
+  if (K <= 0 || Cper <= 0 || f <= 0 || G <= 0 || f > GWTF_MAX_FP || !raw || !packed_w || (training != 0 && training != 1) ||
+      (!packed_film && !training) || pattern0 < 0 || pattern0 > 5)
     return GWTF_E_BADARG;
   const int FP = gwtf_padded_width(f);
   hipStream_t st = (hipStream_t)stream;
   const int threads = 256;
-  if (!stack_only)
-    hipLaunchKernelGGL(pack_scales_kernel, dim3(2 * C), dim3(threads), 0, st, raw, packed_film, C, f, G, FP, training, pattern0, Cper);
+  if (!training)
+    hipLaunchKernelGGL(pack_scales_kernel, dim3(2 * C), dim3(threads), 0, st, raw, packed_film, C, f, G, FP, pattern0, Cper);
   {
     const size_t total = GwtfPackW(FP).coupling_size() * (size_t)C;
     const int blocks = (int)((total + threads - 1) / threads < 2048 ? (total + threads - 1) / threads : 2048);
     hipLaunchKernelGGL(pack_w_kernel, dim3(blocks), dim3(threads), 0, st, raw, packed_film, packed_w, C, f, G, FP, training,
                        pattern0, Cper);
   }
-  if (!stack_only) {
+  if (!training) {
     const size_t total = GwtfPackF(FP, G).coupling_size() * (size_t)C;
     const int blocks = (int)((total + threads - 1) / threads < 2048 ? (total + threads - 1) / threads : 2048);
-    hipLaunchKernelGGL(pack_film_kernel, dim3(blocks), dim3(threads), 0, st, raw, packed_film, C, f, G, FP, training);
+    hipLaunchKernelGGL(pack_film_kernel, dim3(blocks), dim3(threads), 0, st, raw, packed_film, C, f, G, FP);
   }
   return (int)hipGetLastError();
 }

@@ -920,18 +920,6 @@ extern "C" int gwtf_stack_forward_multi(const float* p, const float* packed_w, c
                         p_stride_k, out_stride_k, ex, tune, stream);
 }
 
-// One elementary coupling of the stack (train-mode pipeline: BatchNorm statistics are only known coupling by
-// coupling): applies coupling `c` to p -> out, continues the log-det from logdet_in, optionally writes list
-// slot c and accumulates the coordinate moments of `out` for the next coupling's sd0_bn.
-extern "C" int gwtf_train_apply(const float* p, const float* packed_w, const float* film, float* out,
-                                const float* logdet_in, float* logdet, float* ps, float* mus, float* logvars,
-                                float* moments_out, int c, int B, int N, int C, int f, int pattern0, float eps, int mode,
-                                int tune, void* stream) {
-  const Extras ex = {c, 1, logdet_in, moments_out, 0, 0, nullptr};
-  return stack_dispatch(p, packed_w, film, out, logdet, ps, mus, logvars, nullptr, 1, B, N, C, f, pattern0, eps, mode, 0, 0,
-                        ex, tune, stream);
-}
-
 // One coupling of K stacks in one launch (K-batched train pipeline, gwtf_train.hip): component k reads p + k * p_stride_k,
 // continues logdet + k * out_stride_k, accumulates the next coupling's moments into moments_out + k * moments_stride_k.
 int gwtf_internal_apply_k(const float* p, const float* packed_w, const float* film, float* out, const float* logdet_in,
@@ -997,7 +985,3 @@ int gwtf_internal_stats_k(const float* p, const float* packed_w_c, float* ystats
   }
 }
 
-extern "C" int gwtf_train_stats(const float* p, const float* packed_w_c, float* ystats, int B, int N, int f, int pattern,
-                                int tune, void* stream) {
-  return gwtf_internal_stats_k(p, packed_w_c, ystats, 1, B, N, f, pattern, 0, 0, 0, tune, stream);
-}

@@ -2,8 +2,8 @@
 //
 // In model.train() the four per-point BatchNorm layers of a coupling normalise with statistics over ALL B*N
 // points (reference flows.py:27,30,62,65; nn.BatchNorm1d in training mode), so the stack cannot run as one
-// launch: coupling c+1's statistics depend on coupling c's output.  Per coupling the host enqueues
-//     fold0  ->  stats pass (gwtf_train_stats)  ->  fold1  ->  apply pass (gwtf_train_apply)
+// launch: coupling c+1's statistics depend on coupling c's output.  Per coupling the pipeline (gwtf_mtrain_*, below) enqueues
+//     fold0  ->  stats pass (gwtf_internal_stats_k)  ->  fold1  ->  apply pass (gwtf_internal_apply_k)
 //   fold0: sd0_bn statistics are ANALYTIC in the first and second moments of the kept coordinates
 //          (y0 = W0 x is linear: mean = W0 E[x], var = W0 Cov(x) W0^T), which the previous apply pass
 //          accumulated; folds them into the sd0 record of the packed weights and emits the running-stat update.
@@ -179,14 +179,15 @@ __global__ void fold1_kernel(const float* __restrict__ raw_c, const float* __res
   }
 }
 
-}  // namespace
-
-extern "C" int gwtf_train_moments(const float* p, float* moments, int B, int N, void* stream) {
+// moments [64][16] (replicated accumulators, pre-zeroed) += the 9 moments of the (B,3,N) cloud p
+int train_moments(const float* p, float* moments, int B, int N, void* stream) {
   if (!p || !moments || B <= 0 || N <= 0) return GWTF_E_BADARG;
   const int bx = (N + 256 * 8 - 1) / (256 * 8);
   hipLaunchKernelGGL(moments_kernel, dim3(bx < 1 ? 1 : bx, B), dim3(256), 0, (hipStream_t)stream, p, moments, B, N);
   return (int)hipGetLastError();
 }
+
+}  // namespace
 
 // internal K-batched pieces defined in gwtf_stack.hip / gwtf_bwd.hip
 int gwtf_internal_stats_k(const float* p, const float* packed_w_c, float* ystats, int K, int B, int N, int f, int pattern,
@@ -195,13 +196,6 @@ int gwtf_internal_apply_k(const float* p, const float* packed_w, const float* fi
                           float* logdet, float* ps, float* mus, float* logvars, float* moments_out, size_t moments_stride_k,
                           int c, int K, int B, int N, int C, int f, int pattern0, float eps, int mode, size_t p_stride_k,
                           size_t out_stride_k, int tune, void* stream);
-int gwtf_internal_coupling_backward_k(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
-                                      const float* packed_b_c, const float* film, float* g_in, float* dw1_ws, float* g_film,
-                                      float* g_sd0, float* g_bias, int c, int K, int B, int N, int f, int pattern0, float eps,
-                                      int mode, const GwtfKS& ks, const float* g_ps_c, const float* g_lvs_c, void* stream);
-int gwtf_internal_stats_backward_k(const float* x_in, const float* g_stats, const float* packed_w_c, const float* packed_b_c,
-                                   float* g_in, float* dw1_ws, float* g_sd0, int K, int B, int N, int f, int pattern,
-                                   const GwtfKS& ks, void* stream);
 int gwtf_internal_light_backward_k(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
                                    const float* film, float* g_film, float* g_bias, int c, int K, int B, int N, int f,
                                    int pattern0, float eps, int mode, const GwtfKS& ks, const float* g_ps_c,
@@ -214,37 +208,8 @@ int gwtf_internal_merged_backward_k(const float* x_in, const float* g_out, const
 int gwtf_internal_dw1_reduce_k(float* workspace, int passes, float* dW1, size_t branch_stride, int f, int B, int N, int K,
                                size_t ws_sk, size_t out_sk, void* stream);
 
-namespace {
-GwtfKS single_ks(int C) {
-  GwtfKS ks = {};
-  ks.Cper = ks.Ctot = C;
-  return ks;
-}
-}  // namespace
-
-extern "C" int gwtf_train_fold0(const float* raw_c, const float* moments, double n_total, int pattern, float* packed_w_c,
-                                float* packed_b_c, float* bn_batch_c, int f, int G, void* stream) {
-  if (!raw_c || !moments || !packed_w_c || !bn_batch_c || f <= 0 || f > GWTF_MAX_FP_TRAIN || G <= 0 || pattern < 0 ||
-      pattern > 5 || n_total < 1.0)
-    return GWTF_E_BADARG;
-  hipLaunchKernelGGL(fold0_kernel<GWTF_STAT_REPLICAS>, dim3(1), dim3(2 * GWTF_MAX_FP), 0, (hipStream_t)stream, raw_c, moments, n_total,
-                     pattern, packed_w_c, packed_b_c, bn_batch_c, f, G, gwtf_padded_width(f), single_ks(1));
-  return (int)hipGetLastError();
-}
-
-extern "C" int gwtf_train_fold1(const float* raw_c, const float* ystats, double n_total, const float* film_raw,
-                                float* film_rec, float* bn_batch_c, int c, int B, int C, int f, int G, void* stream) {
-  if (!raw_c || !ystats || !film_raw || !film_rec || !bn_batch_c || f <= 0 || f > GWTF_MAX_FP_TRAIN || G <= 0 || B <= 0 ||
-      c < 0 || c >= C || n_total < 1.0)
-    return GWTF_E_BADARG;
-  hipLaunchKernelGGL(fold1_kernel<GWTF_STAT_REPLICAS>, dim3(B), dim3(2 * GWTF_MAX_FP), 0, (hipStream_t)stream, raw_c, ystats, n_total,
-                     film_raw, film_rec, bn_batch_c, c, C, f, G, gwtf_padded_width(f), single_ks(C));
-  return (int)hipGetLastError();
-}
-
 // =====================================================================================================================
-// Backward of the folds (train mode) and the fused per-coupling train backward.  Same arithmetic as autograd through the
-// torch folds in autograd.py (which remain the multi-rank path); here each fold's backward is ONE small launch.
+// Backward of the folds (train mode): each fold's backward is ONE small launch of the pipeline's backward phases.
 // =====================================================================================================================
 namespace {
 
@@ -503,17 +468,10 @@ __device__ __forceinline__ void fold0_bwd_block(
   }
 }
 
-__global__ __launch_bounds__(kF1Slices * 16) void fold0_bwd_kernel(
-    const float* __restrict__ raw_c, const float* __restrict__ mom_rep, double n_total, int pat,
-    const float* __restrict__ g_sd0, float* __restrict__ g_raw_c, float* __restrict__ gm, int f, int G, int FP,
-    const GwtfKS ks, int NR) {
-  fold0_bwd_block(raw_c, mom_rep, n_total, pat, g_sd0, g_raw_c, gm, f, G, FP, ks, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, NR);
-}
-
 // g_in = g_a [+ g_b: a second pass's share, null when one merged pass wrote g_a] + d(moments)/dx:  gM_a + sum_b Q_ab x_b,
 // Q_aa = 2 gM_aa, Q_ab = gM_ab, with the level's nine moment gradients gM (fold0_bwd_block).  The train pipeline applies this on the
-// fly inside the next level's passes (GwtfCombine); as a pass of its own it is left for the LAST level (dL/dp) and the per-coupling
-// entry point.   block (bx of n_bx = slice of the points, by = shape, bz = mixture component)
+// fly inside the next level's passes (GwtfCombine); as a pass of its own it is left for the LAST level (dL/dp).
+// block (bx of n_bx = slice of the points, by = shape, bz = mixture component)
 __device__ __forceinline__ void combine_block(const float* __restrict__ x, const float* __restrict__ ga,
                                               const float* __restrict__ gb, const float* __restrict__ gm_k,
                                               float* __restrict__ g_in, int B, int N, const GwtfKS& ks, int bx, int by, int bz,
@@ -534,12 +492,6 @@ __device__ __forceinline__ void combine_block(const float* __restrict__ x, const
     g_in[o1] = a1 + g1 + q01 * x0 + q11 * x1 + q12 * x2;
     g_in[o2] = a2 + g2 + q02 * x0 + q12 * x1 + q22 * x2;
   }
-}
-
-__global__ __launch_bounds__(256) void combine_kernel(const float* __restrict__ x, const float* __restrict__ ga,
-                                                      const float* __restrict__ gb, const float* __restrict__ gm,
-                                                      float* __restrict__ g_in, int B, int N, const GwtfKS ks) {
-  combine_block(x, ga, gb, gm, g_in, B, N, ks, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x);
 }
 
 // The tail of a backward level: the sd0 fold's backward (its share of the moment gradients gM feeds the NEXT level's passes, which
@@ -731,7 +683,7 @@ extern "C" int gwtf_mtrain_phase(const GwtfTrainCtx* t, int phase, int step) {
   const int K = t->K, C = t->C, B = t->B, N = t->N, f = t->f, G = t->G, FP = d.FP;
   hipStream_t st = (hipStream_t)t->stream;
   if (phase == GWTF_PHASE_FWD_INIT) {
-    int rc = gwtf_train_moments(t->p, t->moments, B, N, t->stream);
+    int rc = train_moments(t->p, t->moments, B, N, t->stream);
     if (!rc && t->mom_c) compact(t->moments, 0, t->mom_c, 1, 16, st);
     return rc ? rc : (int)hipGetLastError();
   }
@@ -745,12 +697,12 @@ extern "C" int gwtf_mtrain_phase(const GwtfTrainCtx* t, int phase, int step) {
     float* ys_copies = t->ystats + (size_t)c * K * d.YS;
     if (phase == GWTF_PHASE_FWD_A) {
       float* pb_c = t->packed_b ? t->packed_b + (size_t)c * d.PB : nullptr;
-      if (mom.nr == 1)
-        hipLaunchKernelGGL(fold0_kernel<1>, dim3(K), dim3(2 * GWTF_MAX_FP), 0, st, t->raw + (size_t)c * d.RC, mom.p, t->n_total, pat,
-                           t->packed_w + (size_t)c * d.PW, pb_c, t->bn_batch + (size_t)c * d.BS, f, G, FP, ks);
-      else
+      if (mom.nr != 1)     // (this order of the two instantiations keeps both variants' register allocation as it was)
         hipLaunchKernelGGL(fold0_kernel<GWTF_STAT_REPLICAS>, dim3(K), dim3(2 * GWTF_MAX_FP), 0, st, t->raw + (size_t)c * d.RC, mom.p,
                            t->n_total, pat, t->packed_w + (size_t)c * d.PW, pb_c, t->bn_batch + (size_t)c * d.BS, f, G, FP, ks);
+      else
+        hipLaunchKernelGGL(fold0_kernel<1>, dim3(K), dim3(2 * GWTF_MAX_FP), 0, st, t->raw + (size_t)c * d.RC, mom.p, t->n_total, pat,
+                           t->packed_w + (size_t)c * d.PW, pb_c, t->bn_batch + (size_t)c * d.BS, f, G, FP, ks);
       int rc = gwtf_internal_stats_k(cur, t->packed_w + (size_t)c * d.PW, ys_copies, K, B, N, f, pat, ks.x, ks.pw, d.YS, t->tune, t->stream);
       if (!rc && t->ys_c) compact(ys_copies, d.YS, t->ys_c + (size_t)c * K * d.YC, K, (int)d.YC, st);
       return rc ? rc : (int)hipGetLastError();
@@ -929,79 +881,3 @@ extern "C" int gwtf_gather_table(const unsigned long long* table, float* dst, in
 // which half of xbuf / g_bufs holds the final coordinates / dL/dp of component k: base + half * K*B*3*N + k * B*3*N
 extern "C" int gwtf_mtrain_final_forward_half(int C) { return (C - 1) & 1; }
 extern "C" int gwtf_mtrain_final_backward_half(int C, int mode) { return (mode == GWTF_MODE_INVERSE ? C - 1 : 0) & 1; }
-
-// ---- single-stack entry points (the ABI of round 1), now thin wrappers over the K-batched pipeline with K = 1 ----------
-extern "C" int gwtf_train_forward(const float* p, const float* raw, float* packed_w, float* packed_b, const float* film_raw,
-                                  float* moments, float* ystats, float* bn_batch, float* film_rec, float* xbuf,
-                                  float* logdet, float* ps, float* mus, float* logvars, int B, int N, int C, int f, int G,
-                                  int pattern0, float eps, int mode, int tune, void* stream) {
-  GwtfTrainCtx t = {};
-  t.K = 1; t.B = B; t.N = N; t.C = C; t.f = f; t.G = G; t.pattern0 = pattern0; t.mode = mode; t.eps = eps; t.tune = tune;
-  t.n_total = (double)B * N;
-  t.p = p; t.raw = raw; t.packed_w = packed_w; t.packed_b = packed_b; t.film_raw = film_raw; t.film_rec = film_rec;
-  t.moments = moments; t.ystats = ystats; t.bn_batch = bn_batch; t.xbuf = xbuf; t.logdet = logdet;
-  t.ps = ps; t.mus = mus; t.logvars = logvars; t.stream = stream;
-  return gwtf_mtrain_forward(&t);
-}
-
-extern "C" int gwtf_train_backward(const float* p, const float* ps, const float* g_out, const float* g_ld, const float* raw,
-                                   const float* packed_w, const float* packed_b, const float* film_rec, const float* film_raw,
-                                   const float* moments, const float* ystats, float* g_bufs, float* g_xa, float* g_xb,
-                                   float* dw1_ws, float* g_film, float* g_sd0, float* g_bias, float* g_stats, float* g_mom,
-                                   float* g_film_raw, float* g_raw, int* final_buf, int B, int N, int C, int f, int G,
-                                   int pattern0, float eps, int mode, void* stream) {
-  if (!final_buf) return GWTF_E_BADARG;
-  GwtfTrainCtx t = {};
-  t.K = 1; t.B = B; t.N = N; t.C = C; t.f = f; t.G = G; t.pattern0 = pattern0; t.mode = mode; t.eps = eps;
-  t.n_total = (double)B * N;
-  t.p = p; t.raw = raw; t.packed_w = const_cast<float*>(packed_w); t.packed_b = const_cast<float*>(packed_b);
-  t.film_raw = film_raw; t.film_rec = const_cast<float*>(film_rec);
-  t.moments = const_cast<float*>(moments); t.ystats = const_cast<float*>(ystats);
-  // forward-only fields the backward does not touch: any non-null pointer satisfies the context check
-  t.bn_batch = g_stats; t.xbuf = g_bufs; t.logdet = g_xa;
-  t.ps = const_cast<float*>(ps); t.mus = const_cast<float*>(ps); t.logvars = const_cast<float*>(ps);
-  t.g_out = g_out; t.g_ld = g_ld; t.g_bufs = g_bufs; t.g_xa = g_xa; t.g_xb = g_xb; t.dw1_ws = dw1_ws; t.g_film = g_film;
-  t.g_sd0 = g_sd0; t.g_bias = g_bias; t.g_stats = g_stats; t.g_mom = g_mom; t.g_film_raw = g_film_raw; t.g_raw = g_raw;
-  t.stream = stream;
-  *final_buf = gwtf_mtrain_final_backward_half(C, mode);
-  return gwtf_mtrain_backward(&t);
-}
-
-// Backward of ONE coupling of the single-rank train pipeline (kept for the per-coupling autograd nodes and their tests):
-// the three backward phases of the K = 1 pipeline on caller-addressed per-coupling buffers.
-extern "C" int gwtf_train_coupling_backward(const float* x_in, const float* g_out, const float* g_ld, const float* raw_c,
-                                            const float* packed_w_c, const float* packed_b_c, const float* film_rec,
-                                            const float* film_raw, const float* moments_c, const float* ystats_c,
-                                            float* g_in, float* g_xa, float* g_xb, float* dw1_ws, float* g_film, float* g_sd0,
-                                            float* g_bias, float* g_stats, float* g_mom, float* g_film_raw, float* g_raw_c,
-                                            int c, int B, int N, int C, int f, int G, int pattern0, float eps, int mode,
-                                            void* stream) {
-  if (!x_in || !g_out || !g_ld || !raw_c || !packed_w_c || !packed_b_c || !film_rec || !film_raw || !moments_c ||
-      !ystats_c || !g_in || !g_xa || !g_xb || !dw1_ws || !g_film || !g_sd0 || !g_bias || !g_stats || !g_mom ||
-      !g_film_raw || !g_raw_c)
-    return GWTF_E_BADARG;
-  const int FP = gwtf_padded_width(f), pat = (pattern0 + c) % 6;
-  const double n_total = (double)B * N;
-  hipStream_t st = (hipStream_t)stream;
-  const GwtfKS ks = single_ks(C);
-  if (B <= 0 || N <= 0 || C <= 0 || c < 0 || c >= C || f <= 0 || f > GWTF_MAX_FP_TRAIN || pattern0 < 0 || pattern0 > 5 ||
-      (mode != GWTF_MODE_DIRECT && mode != GWTF_MODE_INVERSE))
-    return GWTF_E_BADARG;
-  int rc = gwtf_internal_light_backward_k(x_in, g_out, g_ld, packed_w_c, film_rec, g_film, g_bias, c, 1, B, N, f, pattern0, eps,
-                                          mode, ks, nullptr, nullptr, GwtfCombine{}, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(fold1_bwd_kernel, dim3(2, FP / 16, 1), dim3(kF1Slices * 16), 0, st, raw_c, ystats_c, n_total, film_raw, g_film,
-                     g_bias, g_film_raw, g_raw_c, g_stats, c, B, C, f, G, FP, ks, GWTF_STAT_REPLICAS);
-  rc = gwtf_internal_merged_backward_k(x_in, g_out, g_ld, packed_w_c, packed_b_c, film_rec, g_stats, g_xa, dw1_ws, g_sd0, c, 1, B,
-                                       N, f, pattern0, eps, mode, ks, nullptr, nullptr, GwtfCombine{}, stream);
-  if (rc) return rc;
-  hipError_t me = hipMemsetAsync(g_mom, 0, 16 * sizeof(float), st);   // the nine moment gradients gM, accumulated by the fold's blocks
-  if (me != hipSuccess) return (int)me;
-  hipLaunchKernelGGL(fold0_bwd_kernel, dim3(2, FP / 16, 1), dim3(kF1Slices * 16), 0, st, raw_c, moments_c, n_total, pat, g_sd0,
-                     g_raw_c, g_mom, f, G, FP, ks, GWTF_STAT_REPLICAS);
-  const int bx = (N + 255) / 256;
-  hipLaunchKernelGGL(combine_kernel, dim3(bx < 64 ? bx : 64, B, 1), dim3(256), 0, st, x_in, g_xa, static_cast<const float*>(nullptr),
-                     g_mom, g_in, B, N, ks);
-  const GwtfRaw R(f, G);
-  return gwtf_dw1_reduce(dw1_ws, 1, g_raw_c + R.sd1_w(), R.branch_size(), f, B, N, stream);
-}

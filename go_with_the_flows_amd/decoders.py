@@ -48,10 +48,8 @@ class _SiblingGroup:
         d0 = self.decoders[0]
         if not (p.is_cuda and g.is_cuda) or p.dim() != 3 or p.shape[2] == 0 or os.environ.get('GWTF_NO_SIBLING_BATCH') == '1':
             return False
-        if any(not d.training or (d.n_flows, d.f_n_features, d.g_n_features) != (d0.n_flows, d0.f_n_features, d0.g_n_features)
-               for d in self.decoders):
-            return False
-        return not any(getattr(d.engine(), 'force_autograd_chain', False) for d in self.decoders)
+        return all(d.training and (d.n_flows, d.f_n_features, d.g_n_features) == (d0.n_flows, d0.f_n_features, d0.g_n_features)
+                   for d in self.decoders)
 
     def lists_for(self, dec, p, g, mode):
         """The (ps, mus, logvars) lists of ``dec`` from a batched round, or None: the caller then runs its own pipeline."""
@@ -94,7 +92,6 @@ class _SiblingGroup:
         rnd['pending'].discard(k)
         e = self.decoders[k].engine()
         e._update_running_stats(rnd['bn_batch'][k])        # this decoder's BatchNorm buffers move when ITS call arrives
-        e._last_lists = None
         ps, mus, lvs = rnd['lists']
         res = list(ps[k].unbind(0)), list(mus[k].unbind(0)), list(lvs[k].unbind(0))
         # the slot of the fully transformed cloud IS the pipeline's output tensor (same kernel, same registers): handing that tensor

@@ -358,29 +358,30 @@ class StackEngine:
         return out
 
     def _collect(self):
-        self._key(False)
+        self._key()
         return self._tracked
 
-    def _key(self, training):
+    def _key(self):
         stamp = sum(c._stamp for c in self.couplings)
         if stamp != self._tracked_stamp:  # buffers are re-created by .to()/.cuda(): re-collect
             self._tracked = [t for c in self.couplings for t in c.tracked_tensors()]
             self._tracked_stamp = stamp
-        return (training, stamp, sum(map(_VERSION, self._tracked)))
+        return (stamp, sum(map(_VERSION, self._tracked)))
 
-    def packed(self, training):
-        key = self._key(training)
+    def packed(self):
+        """The eval packing (running statistics folded) of the current parameters, cached until one of them changes."""
+        key = self._key()
         if key != self._cache_key:
             with torch.no_grad():
                 raw = self.raw_arena()
-                self._packed = _lib.pack_weights(raw, self.C, self.f, self.G, training, self.pattern0)
+                self._packed = _lib.pack_weights(raw, self.C, self.f, self.G, False, self.pattern0)
             self._cache_key = key
             self._packed_x = None
         return self._packed
 
     def packed_exact(self):
         """The exact-fp32 operand record of the CURRENT eval packing (cached with it)."""
-        pw, pf = self.packed(False)
+        pw, pf = self.packed()
         if getattr(self, '_packed_x', None) is None:
             with torch.no_grad():
                 self._packed_x = _lib.pack_weights_exact(self.raw_arena(), pf, self.C, self.f, self.G, self.pattern0)
@@ -414,47 +415,24 @@ class StackEngine:
         if (needs_grad or c0.training) and self.f > 96:
             raise NotImplementedError(f'f_n_features={self.f}: train-mode BatchNorm and the backward pass are built for widths up to '
                                       '96 (their LDS working set exceeds 160 KiB beyond); eval-mode forward works up to 128')
-        if needs_grad and c0.training:
-            import torch.distributed as dist
-            multi = _sharded()
-            if not getattr(self, 'force_autograd_chain', False):
-                # the fused pipeline: single rank = two C calls; several ranks = one packed statistic all-reduce per phase
-                from .autograd import train_density_forward_fast
-                out, logdet, lists, bn_batch = train_density_forward_fast(self, p, g, mode, distributed=multi)
-                self._update_running_stats(bn_batch)
-                self._last_lists = None
-                return out, logdet, lists
-            from .autograd import train_density_forward
-            out, logdet, (ps, mus, lvs), bn_batch = train_density_forward(self, p, g, distributed=multi, mode=mode)
+        if c0.training:
+            # batch-statistic BatchNorm, with or without autograd, one rank or several: the fused pipeline (autograd.py
+            # TrainMixtureFn; several ranks all-reduce one packed statistic per phase, as SyncBatchNorm does, train_ae.py:152)
+            from .autograd import train_density_forward_fast
+            out, logdet, lists, bn_batch = train_density_forward_fast(self, p, g, mode, distributed=_sharded(), want_lists=want_lists)
             self._update_running_stats(bn_batch)
-            self._last_lists = (ps, mus, lvs)
-            lists = (torch.stack([t.detach() for t in ps]), torch.stack(mus), torch.stack([t.detach() for t in lvs])) \
-                if want_lists else None
             return out, logdet, lists
-        if needs_grad and not c0.training:
+        if needs_grad:
             # differentiable density pass: HIP forward + HIP backward (autograd.py); every ps[j] / logvars[j] list entry is
             # differentiable as in the reference (decoders.py:61-79); a gradient through a mus[j] entry raises
             from .autograd import density_forward
-            out, logdet, lists = density_forward(self, p, g, mode)
-            self._last_lists = None
-            return out, logdet, lists
+            return density_forward(self, p, g, mode)
         pc, gc = p.contiguous().float(), g.contiguous().float()
         eps = c0._eps_value
-        if c0.training and self.f > 64:
-            # the per-coupling train kernels of this path keep a feature per lane (f <= 64): wider stacks take the fused pipeline
-            from .autograd import train_density_forward_fast
-            with torch.no_grad():
-                out, logdet, lists, bn_batch = train_density_forward_fast(self, pc, gc, mode, distributed=_sharded())
-                self._update_running_stats(bn_batch)
-            return out, logdet, torch.stack(lists) if want_lists else None
-        if c0.training:
-            out, logdet, lists = self._run_train(pc, gc, mode, want_lists)
-        else:
-            pw, pf = self.packed(False)
-            px = self.packed_exact() if (range_rerun() or _lib.EXACT[0]) else None
-            film = _lib.film_forward(gc, pf, self.C, self.f, eps, False)
-            out, logdet, lists = _lib.stack_forward(pc, pw, film, self.C, self.f, self.pattern0, eps, mode, want_lists, packed_x=px)
-        return out, logdet, lists                 # no-grad paths only: both differentiable cases returned above
+        pw, pf = self.packed()
+        px = self.packed_exact() if (range_rerun() or _lib.EXACT[0]) else None
+        film = _lib.film_forward(gc, pf, self.C, self.f, eps)
+        return _lib.stack_forward(pc, pw, film, self.C, self.f, self.pattern0, eps, mode, want_lists, packed_x=px)
 
     # -- train mode: batch-statistic BatchNorm ----------------------------------------------------------
     def _bn_modules(self):
@@ -519,24 +497,6 @@ class StackEngine:
                                                             table.shape[0], self.f, _lib._stream(flat)))
             torch._C._increment_version(touched)      # written through raw pointers: the packed-weight caches key on versions
 
-    def _run_train(self, p, g, mode, want_lists):
-        """model.train() forward without autograd: statistics over all B*N points, running statistics updated with the
-        modules' momentum, unbiased variance (torch semantics).  One rank: everything in HIP from one C call (the FiLM heads'
-        BatchNorm over the B latent rows included).  Several ranks (the reference wraps the model in SyncBatchNorm,
-        train_ae.py:152): the phase-split pipeline with its packed statistic all-reduces, as the differentiable path."""
-        if _sharded():
-            from .autograd import train_density_forward_fast
-            with torch.no_grad():
-                out, logdet, lists, bn_batch = train_density_forward_fast(self, p, g, mode, distributed=True)
-                self._update_running_stats(bn_batch)
-            return out, logdet, (torch.stack(lists) if want_lists else None)
-        with torch.no_grad():
-            raw = self.raw_arena()
-            out, logdet, lists, bn_batch = _lib.train_forward(p, g, raw, self.C, self.f, self.G, self.pattern0,
-                                                              self.couplings[0]._eps_value, mode, want_lists)
-            self._update_running_stats(bn_batch)
-        return out, logdet, lists
-
     def capture(self, p, g, mode, want_lists=False):
         """hipGraph capture of (FiLM + fused stack) on the CURRENT packed weights and on the storage of ``p``/``g``.
 
@@ -553,13 +513,8 @@ class StackEngine:
         return GraphedStack([self], p, g, mode, want_lists)
 
     def run_lists(self, p, g, mode):
-        out, logdet, lists = self.run(p, g, mode, True)
-        ps, mus, lvs = list(lists[0].unbind(0)), list(lists[1].unbind(0)), list(lists[2].unbind(0))
-        if out.requires_grad and self.couplings[0].training and getattr(self, '_last_lists', None) is not None:
-            dps, dmus, dlvs = self._last_lists          # train mode: every ps[j] / logvars[j] is differentiable
-            self._last_lists = None
-            return list(dps), list(dmus), list(dlvs)
-        return ps, mus, lvs
+        _, _, lists = self.run(p, g, mode, True)
+        return list(lists[0].unbind(0)), list(lists[1].unbind(0)), list(lists[2].unbind(0))
 
 
 class GraphedStack:
@@ -570,7 +525,7 @@ class GraphedStack:
     def __init__(self, engines, p, g, mode, want_lists=False, per_engine_p=None):
         self.engines = list(engines)
         self.p, self.g, self.mode = p, g, mode
-        packs = [e.packed(False) for e in self.engines]
+        packs = [e.packed() for e in self.engines]
         pxs = [e.packed_exact() if (range_rerun() or _lib.EXACT[0]) else None for e in self.engines]
         eps = self.engines[0].couplings[0]._eps_value
         ps = per_engine_p if per_engine_p is not None else [p] * len(self.engines)
@@ -578,7 +533,7 @@ class GraphedStack:
         def body():
             res = []
             for e, (pw, pf), px, pk in zip(self.engines, packs, pxs, ps):
-                film = _lib.film_forward(g, pf, e.C, e.f, eps, False)
+                film = _lib.film_forward(g, pf, e.C, e.f, eps)
                 res.append(_lib.stack_forward(pk, pw, film, e.C, e.f, e.pattern0, eps, mode, want_lists, packed_x=px))
             return res
 

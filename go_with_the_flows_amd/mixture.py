@@ -28,7 +28,7 @@ class MixtureStack:
         return (MixtureStack, (self.decoders,))
 
     def packed(self):
-        packs = [e.packed(False) for e in self.engines]
+        packs = [e.packed() for e in self.engines]
         key = tuple(id(pk[0]) for pk in packs)
         if key != self._cat_key:
             self._cat = (torch.cat([pk[0] for pk in packs]), torch.cat([pk[1] for pk in packs]))
@@ -50,7 +50,7 @@ class MixtureStack:
     def _film(self, g):
         pw, pf = self.packed()
         eps = self.engines[0].couplings[0]._eps_value
-        return pw, _lib.film_forward(g, pf, self.K * self.C, self.f, eps, False), eps
+        return pw, _lib.film_forward(g, pf, self.K * self.C, self.f, eps), eps
 
     def forward_all(self, p, g, mode='inverse'):
         """Every component on every point -> (out, logdet), each (K,B,3,N).  Training / density path."""
@@ -58,7 +58,7 @@ class MixtureStack:
         e0._check(p, g)
         needs_grad = torch.is_grad_enabled() and (p.requires_grad or g.requires_grad or any(
             t.requires_grad for d in self.decoders for t in d.parameters()))
-        if e0.couplings[0].training and not any(getattr(e, 'force_autograd_chain', False) for e in self.engines):
+        if e0.couplings[0].training:
             # batch-statistic BatchNorm: all K components through every kernel of the train pipeline together
             # (csrc/gwtf_train.hip, K-batched pipeline); data-parallel runs all-reduce one packed statistic per phase
             import torch.distributed as dist
@@ -69,10 +69,9 @@ class MixtureStack:
                 out, logdet, _, bn_batch = train_density_forward_multi(self.engines, p, g, mode, distributed=multi, want_lists=False)
             for k, e in enumerate(self.engines):
                 e._update_running_stats(bn_batch[k])
-                e._last_lists = None
             return out, logdet
-        if e0.couplings[0].training or needs_grad:
-            # eval BatchNorm with autograd (or the cross-check chain): the per-component differentiable path
+        if needs_grad:
+            # eval BatchNorm with autograd: the per-component differentiable path
             res = [e.run(p, g, mode, False) for e in self.engines]
             return torch.stack([r[0] for r in res]), torch.stack([r[1] for r in res])
         from .flows import range_rerun
@@ -84,11 +83,11 @@ class MixtureStack:
         """Every component on every point, train-mode BatchNorm, WITH the reference's per-coupling lists: -> (out, logdet (K,B,3,N),
         (ps, mus, logvars) each (K, C, B, 3, N) direct-ordered; ps / logvars differentiable in every slot, a gradient through mus
         raises) -- the K list-API decoder calls of flow_mixture.py:163-166 as ONE pass of the K-batched pipeline.  None when that
-        pipeline does not apply (eval-mode BatchNorm, the cross-check chain): the caller then takes the per-decoder route.
+        pipeline does not apply (eval-mode BatchNorm): the caller then takes the per-decoder route.
         defer_running_stats: return bn_batch (K, ...) as a fourth value instead of updating the BatchNorm buffers here."""
         e0 = self.engines[0]
         e0._check(p, g)
-        if not e0.couplings[0].training or any(getattr(e, 'force_autograd_chain', False) for e in self.engines):
+        if not e0.couplings[0].training:
             return None
         from .autograd import train_density_forward_multi
         from .flows import _sharded
@@ -101,7 +100,6 @@ class MixtureStack:
             return out, logdet, lists, bn_batch
         for k, e in enumerate(self.engines):
             e._update_running_stats(bn_batch[k])
-            e._last_lists = None
         return out, logdet, lists
 
     def forward_partition(self, p, g, counts, mode='direct'):

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define GWTF_ABI_VERSION 7
+#define GWTF_ABI_VERSION 8
 #define GWTF_E_BADARG 10001   /* shape / mode / width outside what the kernels support */
 #define GWTF_E_UNSUPPORTED 10002   /* a layer-width list no kernel instantiation was built for */
 #define GWTF_MODE_DIRECT 0    /* sampling direction  base -> data (reference models.py:202) */
@@ -58,41 +58,25 @@ size_t gwtf_film_out_floats(int f);                   /* FiLM output per (shape,
  *                k = 1 or 2 kept coordinates: the packer needs each coupling's k)
  *   packed_w     [C][gwtf_packed_w_coupling_floats]
  *   packed_film  [C][gwtf_packed_film_coupling_floats]
- *   training     0: fold running statistics (model.eval()); 1: leave the per-shape FiLM BatchNorm
- *                un-folded so gwtf_film_forward takes batch statistics (model.train()). */
+ *   training     0: fold running statistics (model.eval()); 1: the train pipeline's packing (model.train()) -- packed_w only, in
+ *                train form (sd1 un-scaled, sd0 records left to the pipeline's fold0); packed_film may be NULL: the pipeline's
+ *                FiLM heads read the raw arena in place (gwtf_film_heads_forward). */
 int gwtf_pack_weights(const float* raw, float* packed_w, float* packed_film,
                       int C, int f, int G, int pattern0, int training, void* stream);
 /* The same for K concatenated stacks of Cper couplings each (the components of a mixture): raw [K][Cper][...], every stack
- * starts again at warp pattern `pattern0`.  training = 2: the train pipeline's packing -- packed_w only (train form), packed_film
- * may be NULL: its FiLM heads read the raw arena in place (gwtf_film_heads_forward). */
+ * starts again at warp pattern `pattern0`. */
 int gwtf_pack_weights_k(const float* raw, float* packed_w, float* packed_film,
                         int K, int Cper, int f, int G, int pattern0, int training, void* stream);
 
-/* Per-shape FiLM conditioning for all C couplings: the four Linear->BN->Swish->Linear heads of each
- * coupling applied to the latent g, then a = eps + exp(w(g)), b' = a*c1 + b(g).
+/* Per-shape FiLM conditioning for all C couplings, eval-mode BatchNorm (the train-mode heads: gwtf_film_heads_forward): the four
+ * Linear->BN->Swish->Linear heads of each coupling applied to the latent g, then a = eps + exp(w(g)), b' = a*c1 + b(g).
  * Replaces T_{mu,logvar}_0_cond_{w,b}(g) and torch.add(eps, torch.exp(.)) in
  * lib/networks/flows.py:100-101,105-106 (modules built at :33-45,68-80).
  *   g        [B][G]
  *   film_out [B][C][gwtf_film_out_floats]
- *   eps      the coupling's `eps` buffer (reference flows.py:21, 1e-6)
- *   training 1: BatchNorm over the B rows uses batch statistics; bn_stats_out (may be NULL)
- *            receives [C][2 branches][2 heads][2][f] = {batch mean, biased batch var}. */
-int gwtf_film_forward(const float* g, const float* packed_film, float* film_out, float* bn_stats_out,
-                      int B, int G, int C, int f, float eps, int training, void* stream);
-
-/* Differentiable train-mode FiLM heads: the BatchNorm over the B latent rows (batch statistics) + swish that sits between a
- * head's two Linear layers -- T_{mu,logvar}_0_cond_{w,b} = Linear, BatchNorm1d, Swish, Linear (lib/networks/flows.py:33-45,68-80)
- * in train() -- as one kernel per direction; the two Linear layers stay batched library products (autograd.py _film_train).
- *   x      [B][M]   first Linear's outputs of all heads, M = (couplings * 2 branches * 2 heads) * f columns
- *   gamma, beta     BatchNorm weight / bias of head (c, branch x, head h), feature j at base + c*stride_c + x*stride_x + h*stride_h + j
- *                   (views of the raw arena, include/gwtf.h RAW ARENA)
- *   forward : y [B][M] = swish(BN(x)), mean / var (biased) / rstd [M]
- *   backward: gx [B][M], ggamma / gbeta [M] from gy [B][M] */
-int gwtf_film_bn_swish_forward(const float* x, const float* gamma, const float* beta, long stride_c, long stride_x, long stride_h,
-                               int f, int B, int M, float* y, float* mean, float* var, float* rstd, void* stream);
-int gwtf_film_bn_swish_backward(const float* x, const float* gy, const float* gamma, const float* beta, long stride_c, long stride_x,
-                                long stride_h, int f, int B, int M, const float* mean, const float* rstd, float* gx, float* ggamma,
-                                float* gbeta, void* stream);
+ *   eps      the coupling's `eps` buffer (reference flows.py:21, 1e-6) */
+int gwtf_film_forward(const float* g, const float* packed_film, float* film_out, int B, int G, int C, int f, float eps,
+                      void* stream);
 
 /* Fused coupling stack: all C elementary couplings applied to every point, with the log-det
  * accumulation.  Replaces LocalCondRNVPDecoder.forward (lib/networks/decoders.py:61-79) ->
@@ -173,83 +157,28 @@ int gwtf_latent_loss_backward(const float* g_out4, const float* z, const float* 
  * The choice minimises resident rounds x the cost of a round of that tile (calibrated, csrc/gwtf_stack.hip tile_cost). */
 int gwtf_stack_plan(const int* segments, int K, int B, int N, int f, int tune, int* out4);
 
-/* ---- train-mode (batch-statistic BatchNorm) forward pipeline, reference flows.py:27,30,62,65 under model.train() ----
- * Per coupling, in processing order (inverse: C-1..0):  fold0 -> stats -> fold1 -> apply.  See csrc/gwtf_train.hip.
- * gwtf_pack_weights(training=1) leaves sd1 un-scaled and the sd0 records empty; gwtf_film_forward(training=1)
- * writes RAW FiLM {a, b} as film_out[B][C][2 branches][2][FP] (NOT the eval record) and the FiLM BatchNorm
- * batch statistics.  n_total = number of points the statistics cover (B*N; summed over ranks when sharded). */
-/* statistic accumulators are replicated GWTF_STAT_REPLICAS (=64) times to spread atomic contention:
- * moments [64][16] (9 used), ystats [64][2][FP][2]; the fold kernels sum the replicas. */
-int gwtf_train_moments(const float* p, float* moments /*pre-zeroed, accumulated*/, int B, int N, void* stream);
-int gwtf_train_fold0(const float* raw_c, const float* moments, double n_total, int pattern, float* packed_w_c,
-                     float* packed_b_c /*may be NULL: backward record, sd0 section*/, float* bn_batch_c /*[2 branches][4 kinds][2][f]: kind 0 <- {mean, unbiased var} of sd0_bn*/,
-                     int f, int G, void* stream);
-int gwtf_train_stats(const float* p, const float* packed_w_c, float* ystats /*pre-zeroed, accumulated*/,
-                     int B, int N, int f, int pattern, int tune, void* stream);
-int gwtf_train_fold1(const float* raw_c, const float* ystats, double n_total, const float* film_raw, float* film_rec,
-                     float* bn_batch_c /*kind 1 <- sd1_bn*/, int c, int B, int C, int f, int G, void* stream);
-int gwtf_train_apply(const float* p, const float* packed_w, const float* film_rec, float* out, const float* logdet_in,
-                     float* logdet, float* ps, float* mus, float* logvars, float* moments_out /*9 or NULL*/,
-                     int c, int B, int N, int C, int f, int pattern0, float eps, int mode, int tune, void* stream);
-
-/* The whole single-rank train-mode forward enqueued from C (moments + 4 launches per coupling); workspace sizes
- * are documented at the definition in csrc/gwtf_train.hip.  Result coordinates end in xbuf[(C-1) & 1]. */
-int gwtf_train_forward(const float* p, const float* raw, float* packed_w, float* packed_b /*may be NULL*/,
-                       const float* film_raw, float* moments,
-                       float* ystats, float* bn_batch, float* film_rec, float* xbuf, float* logdet,
-                       float* ps, float* mus, float* logvars, int B, int N, int C, int f, int G, int pattern0,
-                       float eps, int mode, int tune, void* stream);
-
 /* ---- backward (both directions, BatchNorm as a fixed affine) --------------------------------------------------
  * Autograd of CondRealNVPFlow3D.forward (reference flows.py:95-117 as differentiated by loss.backward(),
  * training.py:54), one coupling per call, in the FOLDED parameters the forward kernel consumes:
  *   W1p [C][2][f][f] = sd1.weight with sd1_bn's scale folded, W0f [C][2][f][2] / c0f [C][2][f] = sd0 with sd0_bn folded,
  *   FiLM record [B][C][6FP+4] = {c, u0, u1} x 2 branches + biases (gwtf_layout.h).
  * gwtf_pack_folded builds the forward record (packed_w) and the backward record (packed_b) from them.
- * gwtf_coupling_backward: x_in = the coupling's input saved by the forward, g_out/g_ld = dL/d(out), dL/d(logdet);
+ * gwtf_coupling_backward_lists: x_in = the coupling's input saved by the forward, g_out/g_ld = dL/d(out), dL/d(logdet);
+ *   g_ps_c = dL/d ps[c], g_lvs_c = dL/d logvars[c], each [B][3][N] or NULL: gradients that enter through the coupling's own list
+ *   slots (the reference's forward returns differentiable per-coupling lists, decoders.py:61-79);
  *   -> g_in [B][3][N]; dw1_ws: per-workgroup partials of dW1p = sum_p dL/dacc(p) relu(sd0)(p)^T, gwtf_dw1_workspace_floats(f,B,N)
  *   floats, summed by gwtf_dw1_reduce; g_film [B][C][2][3][FP] += {dc, du0, du1}; g_sd0 [64][2][3][FP] += {dW0f[:,0], dW0f[:,1], dc0f};
  *   g_bias [64][4] += {db_lv0, db_lv1, db_mu0, db_mu1}   (64 = GWTF_STAT_REPLICAS copies, sum them; all pre-zeroed). */
 size_t gwtf_packed_b_coupling_floats(int f);
 int gwtf_pack_folded(const float* W1p, const float* W0f, const float* c0f, float* packed_w, float* packed_b,
                      int C, int f, void* stream);
-int gwtf_coupling_backward(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
-                           const float* packed_b_c, const float* film, float* g_in, float* dw1_ws, float* g_film,
-                           float* g_sd0, float* g_bias, int c, int B, int N, int C, int f, int pattern0, float eps, int mode,
-                           void* stream);
-
-/* The same with gradients that enter through the coupling's own list slots (the reference's forward returns differentiable
- * per-coupling lists, decoders.py:61-79): g_ps_c = dL/d ps[c], g_lvs_c = dL/d logvars[c], each [B][3][N] or NULL. */
 int gwtf_coupling_backward_lists(const float* x_in, const float* g_out, const float* g_ld, const float* g_ps_c,
                                  const float* g_lvs_c, const float* packed_w_c, const float* packed_b_c, const float* film,
                                  float* g_in, float* dw1_ws, float* g_film, float* g_sd0, float* g_bias, int c, int B, int N,
                                  int C, int f, int pattern0, float eps, int mode, void* stream);
 
-/* Backward records of the train pipeline: W1T sections from the un-scaled sd1 weights (sd0 sections: gwtf_train_fold0). */
+/* Backward records of the train pipeline: W1T sections from the un-scaled sd1 weights (sd0 sections: the pipeline's fold0). */
 int gwtf_pack_w1t(const float* raw, float* packed_b, int C, int f, int G, void* stream);
-/* Backward of ONE coupling of the single-rank train pipeline: light pass (the FiLM-record / bias sums of the coupling path) +
- * fold1 + merged pass (coupling path and statistics path together: everything after dL/dy is linear in it) + fold0 + moments
- * path + dW1 reduction; csrc/gwtf_train.hip, csrc/gwtf_bwd.hip BW_LIGHT / BW_MERGED.  dw1_ws: at least
- * gwtf_dw1_workspace_floats(f, B, N) + gwtf_dw1_reduce_scratch_floats(f) floats.  g_xb is no longer written (one merged pass
- * leaves one gradient buffer, g_xa); the argument stays for ABI stability.  Workspace contract at the definition. */
-int gwtf_train_coupling_backward(const float* x_in, const float* g_out, const float* g_ld, const float* raw_c,
-                                 const float* packed_w_c, const float* packed_b_c, const float* film_rec,
-                                 const float* film_raw, const float* moments_c, const float* ystats_c, float* g_in,
-                                 float* g_xa, float* g_xb, float* dw1_ws, float* g_film, float* g_sd0,
-                                 float* g_bias, float* g_stats, float* g_mom, float* g_film_raw, float* g_raw_c,
-                                 int c, int B, int N, int C, int f, int G, int pattern0, float eps, int mode,
-                                 void* stream);
-
-/* Backward of the whole single-rank train-mode stack (the K = 1 case of gwtf_mtrain_backward: host loop in the library, one call
- * per decoder).  Array layouts at GwtfTrainCtx; *final_buf = which half of g_bufs [2][B][3][N] holds dL/dp.  g_xa / g_xb are no
- * longer written (the gradient combine is applied on the fly by the next level's passes); the arguments stay. */
-int gwtf_train_backward(const float* p, const float* ps, const float* g_out, const float* g_ld, const float* raw,
-                        const float* packed_w, const float* packed_b, const float* film_rec, const float* film_raw,
-                        const float* moments, const float* ystats, float* g_bufs, float* g_xa, float* g_xb,
-                        float* dw1_ws /*gwtf_mtrain_dw1_floats(f, B, N)*/, float* g_film, float* g_sd0, float* g_bias, float* g_stats,
-                        float* g_mom /*[C][16] zero*/, float* g_film_raw, float* g_raw, int* final_buf, int B, int N, int C, int f, int G,
-                        int pattern0, float eps, int mode, void* stream);
-
 /* ---- FiLM conditioning heads under autograd (csrc/gwtf_film_train.hip) -----------------------------------------------------
  * Replaces T_*_0_cond_w / T_*_0_cond_b of every coupling (reference lib/networks/flows.py:33-45, 68-80, evaluated at :100-101,
  * 105-106): Linear(G -> f) -> BatchNorm1d over the latent rows -> Swish -> Linear(f -> f); a = eps + exp(scale head), b = shift head.
@@ -338,12 +267,6 @@ int gwtf_mtrain_forward(const GwtfTrainCtx* ctx);
 int gwtf_mtrain_backward(const GwtfTrainCtx* ctx);
 int gwtf_mtrain_final_forward_half(int C);
 int gwtf_mtrain_final_backward_half(int C, int mode);
-
-/* Backward of gwtf_train_stats: g_stats [2][2][FP] = dL/d{sum y, sum y^2} per branch and feature (replicas already
- * summed by the caller) -> g_in (kept coordinates only); dw1_ws: this pass's dW1 partials (as gwtf_coupling_backward);
- * g_sd0 [64][2][3][FP] +=. */
-int gwtf_stats_backward(const float* x_in, const float* g_stats, const float* packed_w_c, const float* packed_b_c,
-                        float* g_in, float* dw1_ws, float* g_sd0, int B, int N, int f, int pattern, void* stream);
 
 /* The sd1 weight gradient dW1[br][j][i] = sum_p dL/dacc[br][j](p) * h[br][i](p) is accumulated INSIDE the backward kernels
  * (points on the MFMA K axis, csrc/gwtf_bwd.hip); every workgroup leaves a compact [2][f][f] partial in the workspace.
@@ -449,9 +372,8 @@ size_t gwtf_enc_train_units_floats(int layer);
  * tiles of 32 points, [B][ceil(N / 32)][channels][32] + one spare tile (a wave / a k-step takes 32 points x all channels: one contiguous block), NOT in the
  * reference's (B, C, N); only x (B, 3, N) and the pooled (B, 512) outputs keep the reference's layouts. */
 size_t gwtf_enc_train_act_floats(int B, int channels, int N);
-/* W [C[l+1]][C[l]] -> MFMA fragment images of W (forward) and W^T (backward), gwtf_enc_train_units_floats(layer) floats each */
-int gwtf_enc_train_pack(const float* W, float* units_fwd, float* units_bwd, int layer, void* stream);
-/* the same for layers 1, 2, 3 from ONE launch (W_l, forward images uf_l, backward images ub_l) */
+/* W_l [C[l+1]][C[l]] -> MFMA fragment images of W_l (forward, uf_l) and W_l^T (backward, ub_l) for layers 1, 2, 3 from ONE launch,
+ * gwtf_enc_train_units_floats(l) floats each */
 int gwtf_enc_train_pack_all(const float* W1, const float* W2, const float* W3, float* uf1, float* ub1, float* uf2, float* ub2,
                             float* uf3, float* ub3, void* stream);
 /* mom [64][12] += {sum x (3), sum x x^T (xx xy xz yy yz zz), -} over this rank's points */
@@ -485,8 +407,7 @@ int gwtf_enc_train_top(const float* g_pooled, const float* pooled, const float* 
 int gwtf_enc_train_bwd_consts(const float* sums, int layer, double n_total, const float* gamma, const float* aff,
                               const float* gmax, const float* ymax, float* bconst, void* stream);
 /* Top layer: with dy_3 = s gm_3 + Q y_3 + R and y_3 = W_3 a_2,  dL/da_2(p) = M a_2(p) + v + (rows of the arg-max points),
- * M = W_3^T diag(Q) W_3, v = W_3^T R (two small library GEMMs on the caller's side).
- *   gwtf_enc_train_pack_matrix   fragment images of M * 2^k (rows x kdim row-major, here 256 x 256)
+ * M = W_3^T diag(Q) W_3, v = W_3^T R (gwtf_enc_train_mform below: M's fragment images and v in mconst).
  *   gwtf_enc_train_top_scatter   coef [B][512] (times scale [512] when given: coef = gp, scale = s) -> slot_of [B][N] (row of a point, or -1) and
  *                                extra [B][512][256]: row r of shape b = sum of coef[b][c] W_3[c][:] over the channels whose
  *                                arg-max is that point (only the used rows are written); tables: B (2 * 512 + 2) ints of scratch
@@ -494,7 +415,6 @@ int gwtf_enc_train_bwd_consts(const float* sums, int layer, double n_total, cons
  *                                sums [64][3][256] += {sum gm_2, sum gm_2 yhat_2, sum a_2}; gmax2[0] = max |dA2|;
  *                                a2rows [B][512][256] (out): row slot_of[b][n] of shape b = a_2(b, :, n) of every arg-max point n,
  *                                point-major (the kernel has them in registers; other rows are not written) */
-int gwtf_enc_train_pack_matrix(const float* W, float* units, int rows, int kdim, void* stream);
 int gwtf_enc_train_top_scatter(const float* coef, const float* scale, const int* amax, const float* W3, float* extra, int* slot_of,
                                int* tables, int B, int N, void* stream);
 int gwtf_enc_train_backward_top(const float* y2, const float* aff2, const float* units_m, const float* mconst, const float* extra,

@@ -92,22 +92,22 @@ def test_no_cpu_fallback_and_bad_arguments():
     assert L.gwtf_mixture_nll(None, None, None, None, None, None, None, 65, 1, 1, None) == 10001
 
 
-def test_packed_cache_invalidation_rules():
+def test_eval_packing_cache_invalidation_rules():
     d = gw.LocalCondRNVPDecoder(1, 8, 16)
     eng = d.engine()
-    k0 = eng._key(False)
-    assert eng._key(False) == k0
+    k0 = eng._key()
+    assert eng._key() == k0
     with torch.no_grad():
         d.flows[0].nvp1.T_mu_1[1].bias.add_(1.0)          # tracked in-place edit
-    k1 = eng._key(False)
+    k1 = eng._key()
     assert k1 != k0
     d.eval()                                               # train()/eval() bump the stamp (reference optimiser uses .data)
-    k2 = eng._key(False)
+    k2 = eng._key()
     assert k2 != k1
     d.load_state_dict(d.state_dict())
-    assert eng._key(False) != k2
+    assert eng._key() != k2
     d.flows[0].nvp1.invalidate_packed_weights()
-    assert eng._key(False) != k2
+    assert eng._key() != k2
 
 
 def test_library_keeps_no_tuning_state_and_the_tile_plan_follows_rounds():

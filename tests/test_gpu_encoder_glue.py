@@ -32,7 +32,7 @@ def test_stat_compact_is_the_replica_sum(R, n):
 
 
 def unpack_units(units, rows, kdim):
-    """Inverse of the fragment order of enc_train_pack_kernel (gwtf_encoder_train.hip:69): -> hi + lo as a (rows, kdim) float64 matrix."""
+    """Inverse of the fragment order of enc_train_pack_all_kernel (gwtf_encoder_train.hip:66): -> hi + lo as a (rows, kdim) float64 matrix."""
     L = _lib.lib()
     KS = kdim // 32
     u = units.view(torch.float16).view(rows // 16 * KS, 2, 64, 8).double().cpu().numpy()       # [unit][part][lane][e]

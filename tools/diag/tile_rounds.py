@@ -12,8 +12,8 @@ for ppw in (64, 32, 16):
     row = []
     for B in (8, 16, 24, 32, 40, 48, 64, 80, 96, 128):
         p, g = synth_inputs(B, 2048, G, 0); pd, gd = torch.from_numpy(p).cuda(), torch.from_numpy(g).cuda()
-        pw, pf = d.engine().packed(False)
-        film = _lib.film_forward(gd, pf, 3 * L, f, 1e-6, False)
+        pw, pf = d.engine().packed()
+        film = _lib.film_forward(gd, pf, 3 * L, f, 1e-6)
         with torch.no_grad():
             for _ in range(5): _lib.stack_forward(pd, pw, film, 3 * L, f, 0, 1e-6, 'inverse', False)
             e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
