@@ -250,6 +250,61 @@ __device__ __forceinline__ void coupling_body_pipe(const float* __restrict__ L, 
     bhi[br][ks][nb][j0] = hi[0]; bhi[br][ks][nb][j0 + 1] = hi[1];
     blo[br][ks][nb][j0] = lo[0]; blo[br][ks][nb][j0 + 1] = lo[1];
   };
+  // Stage A of the merged widths, written as GROUPS of fragment units in phases (sd0 FMAs of the group, their conversions, their
+  // residuals, the lo conversions): hipcc emitted every unit as one serial chain through one register pair, and each of its
+  // dependent neighbours (v_pk_fma -> v_cvt_pk -> v_fma_mix -> v_cvt_pk) needs a wait state, which it filled with an s_nop -- three
+  // per unit, 60 per branch and wave.  With another unit's instruction between them no filler is needed.  The scheduling barriers
+  // pin the VALU order only (LDS reads and scalar instructions may cross).  Same instructions on the same values: bit-identical.
+  auto unit_group = [&](int br, int u0, int n) {
+    constexpr int GMAX = 4, SB = 0x3F4;      // sched_barrier mask: SALU, VMEM and DS instructions may cross
+    f32x2 pre[GMAX];
+    unsigned hib[GMAX];
+    float r0[GMAX], r1[GMAX];
+    const int per_ks = 4 * NB;
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g) {
+      if (g >= n) continue;
+      const int u = u0 + g;
+      const int ks = u / per_ks < KS - 1 ? u / per_ks : KS - 1;
+      const int rem = u - ks * per_ks, jp = rem / NB, nb = rem % NB, j0 = 2 * jp;
+      const f32x4* sp = reinterpret_cast<const f32x4*>(L + LY::SD0_BASE + br * K::SD0 + q * 24 + ks * 96);
+      const f32x4 wa = sp[j0 >> 2], wb = KEEP2 ? sp[2 + (j0 >> 2)] : f32x4{0.f, 0.f, 0.f, 0.f}, cc = sp[4 + (j0 >> 2)];
+      const f32x2 wa2 = {wa[j0 & 3], wa[(j0 & 3) + 1]}, wb2 = {wb[j0 & 3], wb[(j0 & 3) + 1]}, cc2 = {cc[j0 & 3], cc[(j0 & 3) + 1]};
+      const f32x2 xa2 = {xa[nb], xa[nb]}, xb2 = {xb[nb], xb[nb]};
+      pre[g] = KEEP2 ? __builtin_elementwise_fma(wa2, xa2, __builtin_elementwise_fma(wb2, xb2, cc2))
+                     : __builtin_elementwise_fma(wa2, xa2, cc2);
+    }
+    __builtin_amdgcn_sched_barrier(SB);
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g)
+      if (g < n) asm("v_cvt_pk_f16_f32 %0, |%1|, |%2|" : "=v"(hib[g]) : "v"(pre[g][0]), "v"(pre[g][1]));
+    __builtin_amdgcn_sched_barrier(SB);
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g) {
+      if (g >= n) continue;
+      asm("v_fma_mix_f32 %0, %1, -1.0, |%2| op_sel_hi:[1,0,0]" : "=v"(r0[g]) : "v"(hib[g]), "v"(pre[g][0]));
+      asm("v_fma_mix_f32 %0, %1, -1.0, |%2| op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1[g]) : "v"(hib[g]), "v"(pre[g][1]));
+    }
+    __builtin_amdgcn_sched_barrier(SB);
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g) {
+      if (g >= n) continue;
+      const int u = u0 + g;
+      const int ks = u / per_ks < KS - 1 ? u / per_ks : KS - 1;
+      const int rem = u - ks * per_ks, jp = rem / NB, nb = rem % NB, j0 = 2 * jp;
+      const f16x2 hi = __builtin_bit_cast(f16x2, hib[g]);
+      const f32x2 r = {r0[g], r1[g]};
+      const f16x2 lo = __builtin_convertvector(r, f16x2);
+      if (ks == KS - 1) {
+        f16x8& b = bhi[br][ks][nb];
+        b[0] = hi[0]; b[1] = hi[1]; b[2] = lo[0]; b[3] = lo[1]; b[4] = hi[0]; b[5] = hi[1];
+      } else {
+        bhi[br][ks][nb][j0] = hi[0]; bhi[br][ks][nb][j0 + 1] = hi[1];
+        blo[br][ks][nb][j0] = lo[0]; blo[br][ks][nb][j0 + 1] = lo[1];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(SB);
+  };
   f32x4 acc[2][MB][NB];
   auto triple = [&](int br, int t) {      // t-th (ks, m, nb) triplet of branch br
     const int ks = t / (MB * NB), m = (t / NB) % MB, nb = t % NB;
@@ -315,8 +370,13 @@ __device__ __forceinline__ void coupling_body_pipe(const float* __restrict__ L, 
   // stage A: fragments of branch 0 (LATEFRAG: for its FIRST k-step only, the rest rides behind its own MFMAs)
   constexpr int U0 = LATEFRAG ? 4 * NB : UNITS;                    // items computed up front
   constexpr int T0 = MB * NB;                                      // triplets of one k-step
+  if constexpr (MERGE) {
 #pragma unroll
-  for (int u = 0; u < U0; ++u) unit(0, u);
+    for (int u = 0; u < U0; u += 4) unit_group(0, u, U0 - u < 4 ? U0 - u : 4);
+  } else {
+#pragma unroll
+    for (int u = 0; u < U0; ++u) unit(0, u);
+  }
   // stage B: MFMAs of branch 0; behind them, in this order: the rest of branch 0's fragments, then branch 1's
   constexpr int QB = (UNITS - U0) + UNITS;
   constexpr int PIECES = MB * 8;
