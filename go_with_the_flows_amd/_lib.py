@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GWTF_LIB') or os.path.join(_HERE, 'libgwtf_hip.so')      # GWTF_LIB: an A/B build (tools/ab_build.sh)
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 MODE_DIRECT, MODE_INVERSE = 0, 1
 STAT_REPLICAS = 64   # GWTF_STAT_REPLICAS in csrc/gwtf_layout.h
@@ -26,21 +26,13 @@ _SIGNATURES = {
     'gwtf_packed_w_coupling_floats': (ctypes.c_size_t, [ctypes.c_int]),
     'gwtf_packed_film_coupling_floats': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     'gwtf_film_out_floats': (ctypes.c_size_t, [ctypes.c_int]),
-    'gwtf_pack_weights': (ctypes.c_int, [_c_fp, _c_fp, _c_fp] + [ctypes.c_int] * 5 + [_c_fp]),
     'gwtf_pack_weights_k': (ctypes.c_int, [_c_fp, _c_fp, _c_fp] + [ctypes.c_int] * 6 + [_c_fp]),
     'gwtf_film_forward': (ctypes.c_int, [_c_fp, _c_fp, _c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_float, _c_fp]),
-    'gwtf_stack_forward': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_stack_forward_multi': (ctypes.c_int, [_c_fp] * 8 + [ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 6 +
-                                 [ctypes.c_float, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, _c_fp]),
+    'gwtf_stack_forward': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_packed_x_coupling_floats': (ctypes.c_size_t, [ctypes.c_int]),
     'gwtf_pack_weights_exact': (ctypes.c_int, [_c_fp, _c_fp, _c_fp] + [ctypes.c_int] * 5 + [_c_fp]),
-    'gwtf_stack_forward_exact': (ctypes.c_int, [_c_fp] * 8 + [ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 6 +
-                                 [ctypes.c_float, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_stack_forward_flagging': (ctypes.c_int, [_c_fp] * 8 + [ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 6 +
-                                    [ctypes.c_float, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, _c_fp, ctypes.c_int, _c_fp]),
-    'gwtf_stack_rerun_flagged': (ctypes.c_int, [_c_fp] * 8 + [ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 6 +
-                                 [ctypes.c_float, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, _c_fp, ctypes.c_int, _c_fp]),
+    'gwtf_stack_forward_exact': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'gwtf_latent_loss_workspace_floats': (ctypes.c_int, [ctypes.c_int] * 2),
     'gwtf_latent_loss_forward': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 3 + [ctypes.c_float] * 3 + [_c_fp]),
     'gwtf_latent_loss_backward': (ctypes.c_int, [_c_fp] * 10 + [ctypes.c_int] * 3 + [ctypes.c_float] * 3 + [_c_fp]),
@@ -131,6 +123,17 @@ class TrainCtx(ctypes.Structure):
                     'p', 'raw', 'packed_w', 'packed_b', 'film_raw', 'film_rec', 'moments', 'ystats', 'mom_c', 'ys_c', 'bn_batch', 'xbuf',
                     'logdet', 'ps', 'mus', 'logvars', 'g_out', 'g_ld', 'g_ps', 'g_lvs', 'g_bufs', 'g_xa', 'g_xb', 'dw1_ws', 'g_film', 'g_sd0',
                     'g_bias', 'g_stats', 'g_mom', 'g_film_raw', 'g_raw', 'stream')])
+
+
+class StackArgs(ctypes.Structure):
+    """GwtfStackArgs of include/gwtf.h (everything a stack launch takes): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('p', 'weights', 'film', 'out', 'logdet', 'ps', 'mus', 'logvars')] +
+                [('segments', ctypes.POINTER(ctypes.c_int)), ('worklist', ctypes.c_void_p),
+                 ('p_stride_k', ctypes.c_size_t), ('out_stride_k', ctypes.c_size_t)] +
+                [(n, ctypes.c_int) for n in ('K', 'B', 'N', 'C', 'f', 'pattern0', 'mode', 'tune')] +
+                [('eps', ctypes.c_float), ('stream', ctypes.c_void_p)])
+
+
 EXPORTS = tuple(_SIGNATURES)
 
 # ---- per-call tuning word (include/gwtf.h GWTF_TUNE_*) ------------------------------------------------------------------------
@@ -283,26 +286,30 @@ def _worklist_ptr(packed_x, K, C, f):
     return packed_x.data_ptr() + 4 * n
 
 
-def _rerun_launch(p, packed_x, film, out, logdet, lp, seg, K, C, f, pattern0, eps, mode, p_stride, out_stride, wl):
-    """The exact-fp32 re-run of the tiles the preceding split launch flagged: from its work list, or by looking at every tile."""
-    if wl is None:
-        return _exact_launch(p, packed_x, film, out, logdet, lp, seg, K, C, f, pattern0, eps, mode, p_stride, out_stride, 1)
-    B, _, N = p.shape
-    check(lib().gwtf_stack_rerun_flagged(_ptr(p, 'p'), _ptr(packed_x, 'packed_x'), _ptr(film, 'film'), _ptr(out, 'out'),
-                                         _ptr(logdet, 'logdet'), lp[0], lp[1], lp[2], seg, K, B, N, C, f, pattern0, float(eps),
-                                         _MODES[mode], p_stride, out_stride, wl, _TUNE[0] & 0xffff, _stream(p)))
-
-
-def _exact_launch(p, packed_x, film, out, logdet, lp, seg, K, C, f, pattern0, eps, mode, p_stride, out_stride, only_flagged):
+def _stack_launch(p, packed_w, film, out, logdet, lists, seg, K, C, f, pattern0, eps, mode, out_stride, packed_x):
+    """One stack launch sequence on the record: the exact body alone under EXACT[0]; otherwise the split launch (flagging into the
+    work list behind packed_x when there is one), then -- packed_x given -- the exact re-run of the tiles it flagged."""
     L = lib()
     B, _, N = p.shape
-    check(L.gwtf_stack_forward_exact(_ptr(p, 'p'), _ptr(packed_x, 'packed_x'), _ptr(film, 'film'), _ptr(out, 'out'),
-                                     _ptr(logdet, 'logdet'), lp[0], lp[1], lp[2], seg, K, B, N, C, f, pattern0, float(eps),
-                                     _MODES[mode], p_stride, out_stride, int(only_flagged), _TUNE[0] & 0xffff, _stream(p)))
+    lp = [None] * 3 if lists is None else [lists[i].data_ptr() for i in range(3)]
+    a = StackArgs(_ptr(p, 'p'), _ptr(packed_w, 'packed_w'), _ptr(film, 'film'), _ptr(out, 'out'), _ptr(logdet, 'logdet'), lp[0], lp[1],
+                  lp[2], seg, _worklist_ptr(packed_x, K, C, f), 0, out_stride, K, B, N, C, f, pattern0, _MODES[mode], _TUNE[0],
+                  float(eps), _stream(p))
+    pa = ctypes.addressof(a)
+    with torch.cuda.device(p.device):
+        if EXACT[0]:
+            if packed_x is None:
+                raise GwtfError('exact_fp32: this call site has no exact record (packed_x)')
+            a.weights = _ptr(packed_x, 'packed_x')
+            check(L.gwtf_stack_forward_exact(pa, 0))
+            return
+        check(L.gwtf_stack_forward(pa))
+        if packed_x is not None:
+            a.weights = _ptr(packed_x, 'packed_x')
+            check(L.gwtf_stack_forward_exact(pa, 1))      # from the work list, or (none) by looking at every tile
 
 
 def stack_forward(p, packed_w, film, C, f, pattern0, eps, mode, want_lists, packed_x=None):
-    L = lib()
     B, three, N = p.shape
     if three != 3:
         raise GwtfError(f'p must be (B,3,N), got {tuple(p.shape)}')
@@ -311,24 +318,7 @@ def stack_forward(p, packed_w, film, C, f, pattern0, eps, mode, want_lists, pack
     out = torch.empty_like(p)
     logdet = torch.empty_like(p)
     lists = torch.empty(3, C, B, 3, N, device=p.device, dtype=torch.float32) if want_lists else None
-    lp = [lists[i].data_ptr() for i in range(3)] if want_lists else [None, None, None]
-    with torch.cuda.device(p.device):
-        if EXACT[0]:
-            if packed_x is None:
-                raise GwtfError('exact_fp32: this call site has no exact record (packed_x)')
-            _exact_launch(p, packed_x, film, out, logdet, lp, None, 1, C, f, pattern0, eps, mode, 0, 0, 0)
-            return out, logdet, lists
-        wl = _worklist_ptr(packed_x, 1, C, f)
-        if wl is None:
-            check(L.gwtf_stack_forward(_ptr(p, 'p'), _ptr(packed_w, 'packed_w'), _ptr(film, 'film'), _ptr(out, 'out'),
-                                       _ptr(logdet, 'logdet'), lp[0], lp[1], lp[2], B, N, C, f, pattern0, float(eps),
-                                       _MODES[mode], _TUNE[0], _stream(p)))
-        else:
-            check(L.gwtf_stack_forward_flagging(_ptr(p, 'p'), _ptr(packed_w, 'packed_w'), _ptr(film, 'film'), _ptr(out, 'out'),
-                                                _ptr(logdet, 'logdet'), lp[0], lp[1], lp[2], None, 1, B, N, C, f, pattern0,
-                                                float(eps), _MODES[mode], 0, 0, wl, _TUNE[0], _stream(p)))
-        if packed_x is not None:
-            _rerun_launch(p, packed_x, film, out, logdet, lp, None, 1, C, f, pattern0, eps, mode, 0, 0, wl)
+    _stack_launch(p, packed_w, film, out, logdet, lists, None, 1, C, f, pattern0, eps, mode, 0, packed_x)
     return out, logdet, lists
 
 
@@ -337,7 +327,6 @@ def stack_forward_multi(p, packed_w, film, K, C, f, pattern0, eps, mode, segment
     """K components in one launch.  shared_points=True: every component maps all of p -> outputs (K,B,3,N).
     Otherwise ``segments`` (list of K (begin,end)) partitions the N points among the components -> (B,3,N).
     out / logdet: optional preallocated result tensors (a timing probe brackets the launch alone with them)."""
-    L = lib()
     B, three, N = p.shape
     if three != 3:
         raise GwtfError(f'p must be (B,3,N), got {tuple(p.shape)}')
@@ -366,23 +355,7 @@ def stack_forward_multi(p, packed_w, film, K, C, f, pattern0, eps, mode, segment
             out = make(B, 3, N, device=p.device, dtype=torch.float32)
             logdet = make(B, 3, N, device=p.device, dtype=torch.float32)
         stride = 0
-    with torch.cuda.device(p.device):
-        if EXACT[0]:
-            if packed_x is None:
-                raise GwtfError('exact_fp32: this call site has no exact record (packed_x)')
-            _exact_launch(p, packed_x, film, out, logdet, [None] * 3, seg, K, C, f, pattern0, eps, mode, 0, stride, 0)
-            return out, logdet
-        wl = _worklist_ptr(packed_x, K, C, f)
-        if wl is None:
-            check(L.gwtf_stack_forward_multi(_ptr(p, 'p'), _ptr(packed_w, 'packed_w'), _ptr(film, 'film'), _ptr(out, 'out'),
-                                             _ptr(logdet, 'logdet'), None, None, None, seg, K, B, N, C, f, pattern0,
-                                             float(eps), _MODES[mode], 0, stride, _TUNE[0], _stream(p)))
-        else:
-            check(L.gwtf_stack_forward_flagging(_ptr(p, 'p'), _ptr(packed_w, 'packed_w'), _ptr(film, 'film'), _ptr(out, 'out'),
-                                                _ptr(logdet, 'logdet'), None, None, None, seg, K, B, N, C, f, pattern0,
-                                                float(eps), _MODES[mode], 0, stride, wl, _TUNE[0], _stream(p)))
-        if packed_x is not None:
-            _rerun_launch(p, packed_x, film, out, logdet, [None] * 3, seg, K, C, f, pattern0, eps, mode, 0, stride, wl)
+    _stack_launch(p, packed_w, film, out, logdet, None, seg, K, C, f, pattern0, eps, mode, stride, packed_x)
     return out, logdet
 
 
@@ -416,7 +389,7 @@ def mixture_nll(z, logdet, mu0, lv0, logits, want_point_lse=False):
 
 
 def stack_plan(K, B, N, f, segments=None, word=None):
-    """The tile plan gwtf_stack_forward* would use (no launch): (points per wave, workgroups) -- host-only, works without a GPU."""
+    """The tile plan gwtf_stack_forward would use (no launch): (points per wave, workgroups) -- host-only, works without a GPU."""
     seg = None
     if segments is not None:
         flat = [int(v) for be in segments for v in be]

@@ -1,7 +1,9 @@
-// gwtf_device.h -- device-side building blocks shared by the forward (gwtf_stack.hip) and backward
-// (gwtf_bwd.hip) kernels: tile configuration, the split-f16 sd1 contraction, the quarter transpose-reduce.
+// gwtf_device.h -- building blocks shared by the forward (gwtf_stack.hip, gwtf_stack_exact.hip) and backward
+// (gwtf_bwd.hip) kernels: tile configuration, the split-f16 sd1 contraction, the quarter transpose-reduce; the host side the two
+// stack sources share (tile list, argument check, instantiation pick); the prototypes of the train pipeline's internal launches.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "gwtf_layout.h"
 #include "../../include/gwtf.h"
 
@@ -315,4 +317,95 @@ __device__ __forceinline__ void sd1_contract(const float* __restrict__ L, int br
     }
 }
 
+// The per-point tail (softsign, scale = sqrt(eps + exp(logvar)), inverse affine) on the hardware's reciprocal, square root
+// and exp2 units (each within 1-2 ulp) instead of correctly rounded division / sqrtf / libm expf: 2 + 1 + 2 instructions
+// against ~11 + ~12 + ~10 per use, 40-75 VALU per coupling and wave.  Operand ranges make the fast forms safe (divisors
+// >= ~0.6, logvar in (-1, 1) by the softsign).  Measured against the reference's own fp64 evaluation on the golden decoder
+// cases (tools/diag/err_vs_fp64.py): mean coordinate error 3.97e-7 / 3.94e-7 (direct / inverse) against 3.75e-7 / 3.95e-7
+// with the correctly rounded forms and 2.81e-7 / 3.36e-7 for the reference's fp32 evaluation itself -- inside the
+// noise of fp32 evaluation order, far inside the stated tolerance (2e-5); airplane kernel 0.522 -> 0.498 ms.
+__device__ __forceinline__ float tail_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
+__device__ __forceinline__ float tail_scale(float eps, float logvar) { return __builtin_amdgcn_sqrtf(eps + __expf(logvar)); }
+// INVERSE mode divides by the scale: 1 / sqrt(eps + exp(logvar)) is ONE hardware op (v_rsq_f32) instead of a square root and a
+// reciprocal in a row -- one transcendental less on the coupling boundary's dependent chain, and none per coordinate
+__device__ __forceinline__ float tail_rscale(float eps, float logvar) { return __builtin_amdgcn_rsqf(eps + __expf(logvar)); }
+
+// ---- the tile list of a stack launch (gwtf_stack.hip, gwtf_stack_exact.hip) ---------------------------------------------------------
+// Component k owns the points [begin[k], end[k]) of every shape; its workgroups are tiles_cum[k] .. tiles_cum[k + 1].
+struct Jobs {
+  int K;
+  int tiles_cum[GWTF_MAX_COMPONENTS + 1];  // prefix sum of B * tiles(k)
+  int begin[GWTF_MAX_COMPONENTS], end[GWTF_MAX_COMPONENTS];
+};
+// pts_wg points per tile, a workgroup walking tpw consecutive tiles of one shape
+inline Jobs make_jobs(const GwtfStackArgs& a, int pts_wg, int tpw = 1) {
+  Jobs jobs;
+  jobs.K = a.K;
+  jobs.tiles_cum[0] = 0;
+  for (int k = 0; k < a.K; ++k) {
+    jobs.begin[k] = a.segments ? a.segments[2 * k] : 0;
+    jobs.end[k] = a.segments ? a.segments[2 * k + 1] : a.N;
+    const int cnt = jobs.end[k] - jobs.begin[k];
+    jobs.tiles_cum[k + 1] = jobs.tiles_cum[k] + a.B * (((cnt + pts_wg - 1) / pts_wg + tpw - 1) / tpw);
+  }
+  return jobs;
+}
+// tile id -> component, shape and tile of that component's [n_begin, n_end), PTS_WG points per tile (one tile per id: tpw = 1).
+// `jobs` by value: it is the kernel's own argument, and by reference the exact kernel's register allocation moves.
+struct TileOf { int comp, b, tile, n_begin, n_end; };
+template <int PTS_WG>
+__device__ __forceinline__ TileOf tile_of(const Jobs jobs, const int bid) {
+  int comp = 0;
+  while (comp + 1 < jobs.K && bid >= jobs.tiles_cum[comp + 1]) ++comp;
+  const int n_begin = jobs.begin[comp], n_end = jobs.end[comp];
+  const int tiles_per_shape = (n_end - n_begin + PTS_WG - 1) / PTS_WG;
+  const int local = bid - jobs.tiles_cum[comp];
+  const int b = local / tiles_per_shape, tile = local - b * tiles_per_shape;
+  return TileOf{comp, b, tile, n_begin, n_end};
+}
+// What both entry points reject before anything is launched.  ps_alone: the coordinate list without the other two is accepted (the
+// train pipeline's fused consumers keep ps only).
+inline bool stack_args_ok(const GwtfStackArgs* a, bool ps_alone) {
+  if (!a || a->B <= 0 || a->N <= 0 || a->C <= 0 || a->f <= 0 || a->f > GWTF_MAX_FP || a->K <= 0 || a->K > GWTF_MAX_COMPONENTS ||
+      !a->p || !a->weights || !a->film || !a->out || !a->logdet)
+    return false;
+  if ((a->mode != GWTF_MODE_DIRECT && a->mode != GWTF_MODE_INVERSE) || a->pattern0 < 0 || a->pattern0 > 5) return false;
+  const bool any = a->ps || a->mus || a->logvars, all = a->ps && a->mus && a->logvars;
+  if (any && !all && !(ps_alone && a->ps && !a->mus && !a->logvars)) return false;
+  for (int k = 0; a->segments && k < a->K; ++k)
+    if (a->segments[2 * k] < 0 || a->segments[2 * k + 1] < a->segments[2 * k] || a->segments[2 * k + 1] > a->N) return false;
+  return true;
+}
+// fn(MODE, LISTS) with the run-time direction and `lists` as compile-time constants: the kernels' <.., MODE, LISTS> instantiation
+template <class F>
+inline void with_mode_lists(int mode, bool lists, F&& fn) {
+  using D = std::integral_constant<int, GWTF_MODE_DIRECT>;
+  using I = std::integral_constant<int, GWTF_MODE_INVERSE>;
+  if (mode == GWTF_MODE_DIRECT) {
+    if (lists) fn(D{}, std::true_type{}); else fn(D{}, std::false_type{});
+  } else {
+    if (lists) fn(I{}, std::true_type{}); else fn(I{}, std::false_type{});
+  }
+}
+
 }  // namespace gwtf_dev
+
+// ---- internal launches of the K-batched train pipeline (gwtf_train.hip calls them) ---------------------------------------------------
+// gwtf_stack.hip: the statistics pass of one coupling of K stacks (component k: p + k*p_sk, packed_w_c + k*pw_sk, ystats + k*ys_sk) ...
+int gwtf_internal_stats_k(const float* p, const float* packed_w_c, float* ystats, int K, int B, int N, int f, int pattern,
+                          size_t p_sk, size_t pw_sk, size_t ys_sk, int tune, void* stream);
+// ... and coupling c alone of the K stacks of `a` in one launch: component k continues logdet_in + k * out_stride_k (null: starts at
+// zero) and accumulates the next coupling's moments into moments_out + k * moments_stride_k (null: none).
+int gwtf_internal_apply_k(const GwtfStackArgs& a, int c, const float* logdet_in, float* moments_out, size_t moments_stride_k);
+// gwtf_bwd.hip
+int gwtf_internal_light_backward_k(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
+                                   const float* film, float* g_film, float* g_bias, int c, int K, int B, int N, int f,
+                                   int pattern0, float eps, int mode, const GwtfKS& ks, const float* g_ps_c,
+                                   const float* g_lvs_c, const GwtfCombine& cmb, void* stream);
+int gwtf_internal_merged_backward_k(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
+                                    const float* packed_b_c, const float* film, const float* g_stats, float* g_in, float* dw1_ws,
+                                    float* g_sd0, int c, int K, int B, int N, int f, int pattern0, float eps, int mode,
+                                    const GwtfKS& ks, const float* g_ps_c, const float* g_lvs_c, const GwtfCombine& cmb,
+                                    void* stream);
+int gwtf_internal_dw1_reduce_k(float* workspace, int passes, float* dW1, size_t branch_stride, int f, int B, int N, int K,
+                               size_t ws_sk, size_t out_sk, void* stream);

@@ -279,8 +279,3 @@ extern "C" int gwtf_pack_weights_k(const float* raw, float* packed_w, float* pac
   }
   return (int)hipGetLastError();
 }
-
-extern "C" int gwtf_pack_weights(const float* raw, float* packed_w, float* packed_film, int C, int f, int G,
-                                 int pattern0, int training, void* stream) {
-  return gwtf_pack_weights_k(raw, packed_w, packed_film, 1, C, f, G, pattern0, training, stream);
-}

@@ -27,19 +27,6 @@ namespace {
 
 using namespace gwtf_dev;
 
-// The per-point tail (softsign, scale = sqrt(eps + exp(logvar)), inverse affine) on the hardware's reciprocal, square root
-// and exp2 units (each within 1-2 ulp) instead of correctly rounded division / sqrtf / libm expf: 2 + 1 + 2 instructions
-// against ~11 + ~12 + ~10 per use, 40-75 VALU per coupling and wave.  Operand ranges make the fast forms safe (divisors
-// >= ~0.6, logvar in (-1, 1) by the softsign).  Measured against the reference's own fp64 evaluation on the golden decoder
-// cases (tools/diag/err_vs_fp64.py): mean coordinate error 3.97e-7 / 3.94e-7 (direct / inverse) against 3.75e-7 / 3.95e-7
-// with the correctly rounded forms and 2.81e-7 / 3.36e-7 for the reference's fp32 evaluation itself -- inside the
-// noise of fp32 evaluation order, far inside the stated tolerance (2e-5); airplane kernel 0.522 -> 0.498 ms.
-__device__ __forceinline__ float tail_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
-__device__ __forceinline__ float tail_scale(float eps, float logvar) { return __builtin_amdgcn_sqrtf(eps + __expf(logvar)); }
-// INVERSE mode divides by the scale: 1 / sqrt(eps + exp(logvar)) is ONE hardware op (v_rsq_f32) instead of a square root and a
-// reciprocal in a row -- one transcendental less on the coupling boundary's dependent chain, and none per coordinate
-__device__ __forceinline__ float tail_rscale(float eps, float logvar) { return __builtin_amdgcn_rsqf(eps + __expf(logvar)); }
-
 // Where the pieces of one staged coupling sit in LDS (floats).  Plain: the packed record as it is in global memory
 // (gwtf_layout.h GwtfPackW) followed by the shape's FiLM record.  COMPACT (merged widths f = 33..40, MB = 3): the packer leaves
 // the lo image of the second k-step unused there (its products ride in the merged hi image A'), so those MB pieces per branch
@@ -551,13 +538,7 @@ struct Extras {
   float* moments_out;            // [GWTF_STAT_REPLICAS][16], 9 used {Sx0,Sx1,Sx2,Sx0x0,Sx0x1,Sx0x2,Sx1x1,Sx1x2,Sx2x2}, or null
   size_t moments_stride_k;       // component k accumulates into moments_out + k * moments_stride_k
   int tpw;                       // one-coupling launches: consecutive tiles of ONE shape a workgroup walks (0 / 1 = one tile)
-  int* worklist;                 // null, or the flagged-wave list a gwtf_stack_rerun_flagged launch reads (include/gwtf.h)
-};
-
-struct Jobs {
-  int K;
-  int tiles_cum[GWTF_MAX_COMPONENTS + 1];  // prefix sum of B * tiles(k)
-  int begin[GWTF_MAX_COMPONENTS], end[GWTF_MAX_COMPONENTS];
+  int* worklist;                 // null, or the flagged-wave list the exact re-run launch reads (GwtfStackArgs.worklist)
 };
 
 template <int MB, int NB, int MODE, bool LISTS, int NJL = 0>
@@ -780,69 +761,41 @@ __global__ __launch_bounds__(256) void stack_kernel(const float* __restrict__ p,
 }
 
 template <int MB, int NB>
-int launch(const float* p, const float* pw, const float* film, float* out, float* logdet, float* ps, float* mus,
-           float* lvs, int B, int N, int C, int pattern0, float eps, int mode, int kk_steps, const int* segs, int K,
-           size_t p_stride_k, size_t out_stride_k, const Extras& ex, bool pipe, hipStream_t st) {
-  Jobs jobs;
-  jobs.K = K;
-  jobs.tiles_cum[0] = 0;
-  for (int k = 0; k < K; ++k) {
-    jobs.begin[k] = segs ? segs[2 * k] : 0;
-    jobs.end[k] = segs ? segs[2 * k + 1] : N;
-    const int cnt = jobs.end[k] - jobs.begin[k];
-    const int tpw = ex.tpw > 1 ? ex.tpw : 1;
-    jobs.tiles_cum[k + 1] = jobs.tiles_cum[k] + B * (((cnt + 64 * NB - 1) / (64 * NB) + tpw - 1) / tpw);
-  }
-  if (jobs.tiles_cum[K] == 0) return 0;
-  const dim3 grid((unsigned)jobs.tiles_cum[K]), block(256);
-  const bool lists = ps != nullptr;
-#define GWTF_LAUNCH(MODE_, LISTS_)                                                                                      \
-  hipLaunchKernelGGL((stack_kernel<MB, NB, MODE_, LISTS_>), grid, block, 0, st, p, pw, film, out, logdet, ps, mus, lvs, \
-                     B, N, C, pattern0, eps, kk_steps, jobs, p_stride_k, out_stride_k, ex)
-  // Software-pipelined body (coupling_body_pipe) for the widths the reference's configs resolve to -- the number of valid
+int launch(const GwtfStackArgs& a, int kk_steps, const Extras& ex, bool pipe) {
+  const Jobs jobs = make_jobs(a, 64 * NB, ex.tpw > 1 ? ex.tpw : 1);
+  if (jobs.tiles_cum[a.K] == 0) return 0;
+  const dim3 grid((unsigned)jobs.tiles_cum[a.K]), block(256);
+  // NJL_ > 0: the software-pipelined body (coupling_body_pipe), 0: the run-time-width one
+  auto run = [&](auto NJL_) {
+    with_mode_lists(a.mode, a.ps != nullptr, [&](auto MODE_, auto LISTS_) {
+      hipLaunchKernelGGL((stack_kernel<MB, NB, decltype(MODE_)::value, decltype(LISTS_)::value, decltype(NJL_)::value>), grid, block,
+                         0, (hipStream_t)a.stream, a.p, a.weights, a.film, a.out, a.logdet, a.ps, a.mus, a.logvars, a.B, a.N, a.C,
+                         a.pattern0, a.eps, kk_steps, jobs, a.p_stride_k, a.out_stride_k, ex);
+    });
+    return (int)hipGetLastError();
+  };
+  // Software-pipelined body for the widths the reference's configs resolve to -- the number of valid
   // k-slots of the last k-step must be a compile-time fact: f = 61..64 (NJL 8), 37..40 (2), 33..36 (1), 17..20 (5) -- and
   // for the tiles whose fragments + both branches' accumulators fit 256 VGPRs.
   const int njl = kk_steps - 8 * (Cfg<MB>::KS - 1);
-#define GWTF_PIPED(NJL_)                                                                                                    \
-  if (njl == NJL_) {                                                                                                        \
-    if (mode == GWTF_MODE_DIRECT) {                                                                                         \
-      if (lists) hipLaunchKernelGGL((stack_kernel<MB, NB, GWTF_MODE_DIRECT, true, NJL_>), grid, block, 0, st, p, pw, film, out, logdet, ps, mus, lvs, B, N, C, pattern0, eps, kk_steps, jobs, p_stride_k, out_stride_k, ex);   \
-      else hipLaunchKernelGGL((stack_kernel<MB, NB, GWTF_MODE_DIRECT, false, NJL_>), grid, block, 0, st, p, pw, film, out, logdet, ps, mus, lvs, B, N, C, pattern0, eps, kk_steps, jobs, p_stride_k, out_stride_k, ex);        \
-    } else {                                                                                                                \
-      if (lists) hipLaunchKernelGGL((stack_kernel<MB, NB, GWTF_MODE_INVERSE, true, NJL_>), grid, block, 0, st, p, pw, film, out, logdet, ps, mus, lvs, B, N, C, pattern0, eps, kk_steps, jobs, p_stride_k, out_stride_k, ex);  \
-      else hipLaunchKernelGGL((stack_kernel<MB, NB, GWTF_MODE_INVERSE, false, NJL_>), grid, block, 0, st, p, pw, film, out, logdet, ps, mus, lvs, B, N, C, pattern0, eps, kk_steps, jobs, p_stride_k, out_stride_k, ex);       \
-    }                                                                                                                       \
-    return (int)hipGetLastError();                                                                                          \
-  }
   if (pipe) {
-    if constexpr (MB == 4 && NB <= 2) { GWTF_PIPED(8) }
-    if constexpr (MB == 3) { GWTF_PIPED(2) GWTF_PIPED(1) }
-    if constexpr (MB == 2) { GWTF_PIPED(5) }
+    if constexpr (MB == 4 && NB <= 2) { if (njl == 8) return run(std::integral_constant<int, 8>{}); }
+    if constexpr (MB == 3) {
+      if (njl == 2) return run(std::integral_constant<int, 2>{});
+      if (njl == 1) return run(std::integral_constant<int, 1>{});
+    }
+    if constexpr (MB == 2) { if (njl == 5) return run(std::integral_constant<int, 5>{}); }
   }
-#undef GWTF_PIPED
-  if (mode == GWTF_MODE_DIRECT) {
-    if (lists) GWTF_LAUNCH(GWTF_MODE_DIRECT, true); else GWTF_LAUNCH(GWTF_MODE_DIRECT, false);
-  } else {
-    if (lists) GWTF_LAUNCH(GWTF_MODE_INVERSE, true); else GWTF_LAUNCH(GWTF_MODE_INVERSE, false);
-  }
-#undef GWTF_LAUNCH
-  return (int)hipGetLastError();
+  return run(std::integral_constant<int, 0>{});
 }
 
 template <int MB>
-int launch_nb(int nb, const float* p, const float* pw, const float* film, float* out, float* logdet, float* ps,
-              float* mus, float* lvs, int B, int N, int C, int pattern0, float eps, int mode, int kk_steps,
-              const int* segs, int K, size_t p_stride_k, size_t out_stride_k, const Extras& ex, bool pipe, hipStream_t st) {
-  if constexpr (MB > 4) {      // f > 64: one workgroup per compute unit anyway (LDS); 16 or 32 points per wave keep the accumulators in registers
-    if (nb == 1) return launch<MB, 1>(p, pw, film, out, logdet, ps, mus, lvs, B, N, C, pattern0, eps, mode, kk_steps, segs, K, p_stride_k, out_stride_k, ex, pipe, st);
-    return launch<MB, 2>(p, pw, film, out, logdet, ps, mus, lvs, B, N, C, pattern0, eps, mode, kk_steps, segs, K, p_stride_k, out_stride_k, ex, pipe, st);
-  } else {
-  switch (nb) {
-    case 1: return launch<MB, 1>(p, pw, film, out, logdet, ps, mus, lvs, B, N, C, pattern0, eps, mode, kk_steps, segs, K, p_stride_k, out_stride_k, ex, pipe, st);
-    case 2: return launch<MB, 2>(p, pw, film, out, logdet, ps, mus, lvs, B, N, C, pattern0, eps, mode, kk_steps, segs, K, p_stride_k, out_stride_k, ex, pipe, st);
-    default: return launch<MB, 4>(p, pw, film, out, logdet, ps, mus, lvs, B, N, C, pattern0, eps, mode, kk_steps, segs, K, p_stride_k, out_stride_k, ex, pipe, st);
-  }
-  }
+int launch_nb(int nb, const GwtfStackArgs& a, int kk_steps, const Extras& ex, bool pipe) {
+  // f > 64: one workgroup per compute unit anyway (LDS); 16 or 32 points per wave keep the accumulators in registers
+  constexpr int NB_MAX = MB > 4 ? 2 : 4;
+  if (nb == 1) return launch<MB, 1>(a, kk_steps, ex, pipe);
+  if (nb == 2) return launch<MB, 2>(a, kk_steps, ex, pipe);
+  return launch<MB, NB_MAX>(a, kk_steps, ex, pipe);
 }
 
 // ---- tile choice -------------------------------------------------------------------------------------------------------------
@@ -904,98 +857,59 @@ extern "C" int gwtf_stack_plan(const int* segments, int K, int B, int N, int f, 
   return 0;
 }
 
-static int stack_dispatch(const float* p, const float* packed_w, const float* film, float* out, float* logdet, float* ps,
-                          float* mus, float* logvars, const int* segments, int K, int B, int N, int C, int f,
-                          int pattern0, float eps, int mode, size_t p_stride_k, size_t out_stride_k, const Extras& ex_in,
-                          int tune, void* stream) {
-  if (B <= 0 || N <= 0 || C <= 0 || f <= 0 || f > GWTF_MAX_FP || K <= 0 || K > GWTF_MAX_COMPONENTS || !p ||
-      !packed_w || !film || !out || !logdet)
-    return GWTF_E_BADARG;
-  if (mode != GWTF_MODE_DIRECT && mode != GWTF_MODE_INVERSE) return GWTF_E_BADARG;
-  if (pattern0 < 0 || pattern0 > 5) return GWTF_E_BADARG;
-  if (ex_in.c_count < 0 || (ex_in.c_count > 0 && (ex_in.c_first < 0 || ex_in.c_first >= C))) return GWTF_E_BADARG;
-  const bool any = ps || mus || logvars, all = ps && mus && logvars, ps_only = ps && !mus && !logvars;
-  if (any && !all && !ps_only) return GWTF_E_BADARG;     // the three lists, none, or the coordinates alone (train pipeline)
-  long pts = 0;
-  for (int k = 0; k < K; ++k) {
-    const int b0 = segments ? segments[2 * k] : 0, e0 = segments ? segments[2 * k + 1] : N;
-    if (b0 < 0 || e0 < b0 || e0 > N) return GWTF_E_BADARG;
-    pts += (long)B * (e0 - b0);
-  }
-  hipStream_t st = (hipStream_t)stream;
+static int stack_dispatch(const GwtfStackArgs* args, const Extras& ex_in) {
+  if (!stack_args_ok(args, true)) return GWTF_E_BADARG;
+  const GwtfStackArgs& a = *args;
+  if (ex_in.c_count < 0 || (ex_in.c_count > 0 && (ex_in.c_first < 0 || ex_in.c_first >= a.C))) return GWTF_E_BADARG;
+  const int f = a.f, tune = a.tune;
   // points per wave.  Whole-stack launches: the tile whose rounds x round cost is smallest (choose_nb).  One-coupling launches of
   // the train pipeline (ex.c_count == 1) are latency-bound per launch whatever the tile: the largest tile that still gives each
   // of the 1024 SIMDs two waves.
   int nb;
   const int forced = (tune & 0xffff) / 16;
   if (ex_in.c_count == 0 || forced == 1 || forced == 2 || forced == 4) {
-    nb = choose_nb(segments, K, B, N, f, tune);
+    nb = choose_nb(a.segments, a.K, a.B, a.N, f, tune);
   } else {
+    long pts = 0;
+    for (int k = 0; k < a.K; ++k) pts += (long)a.B * (a.segments ? a.segments[2 * k + 1] - a.segments[2 * k] : a.N);
     nb = pts >= 2048L * 64 ? 4 : (pts >= 2048L * 32 ? 2 : 1);
     if (f > 64 && nb > 2) nb = 2;
   }
   Extras ex = ex_in;
   ex.tpw = 1;
-  if (ex.c_count == 1 && !segments && !(tune & GWTF_TUNE_SINGLE_TILE)) {
+  if (ex.c_count == 1 && !a.segments && !(tune & GWTF_TUNE_SINGLE_TILE)) {
     // one-coupling launch on a grid of several rounds: as many tiles of a shape per workgroup as still leave every resident slot
     // a workgroup (the staging of the coupling is then paid once per slot, not once per tile)
     const int MBi = gwtf_padded_width(f) / 16;
     const TileCost tc = tile_cost(MBi, nb == 4 ? 2 : nb - 1);
-    const long tps = (N + 64 * nb - 1) / (64 * nb), total = (long)K * B * tps;
+    const long tps = (a.N + 64 * nb - 1) / (64 * nb), total = (long)a.K * a.B * tps;
     ex.tpw = (int)std::max(1L, std::min(tps, total / (256L * tc.slots)));
   }
   const bool pipe = !(tune & GWTF_TUNE_GENERIC_BODY);
   const int kk_steps = (f + 3) / 4;
-#define GWTF_ARGS nb, p, packed_w, film, out, logdet, ps, mus, logvars, B, N, C, pattern0, eps, mode, kk_steps, segments, K, p_stride_k, out_stride_k, ex, pipe, st
   switch (gwtf_padded_width(f) / 16) {
-    case 1: return launch_nb<1>(GWTF_ARGS);
-    case 2: return launch_nb<2>(GWTF_ARGS);
-    case 3: return launch_nb<3>(GWTF_ARGS);
-    case 4: return launch_nb<4>(GWTF_ARGS);
-    case 5: return launch_nb<5>(GWTF_ARGS);
-    case 6: return launch_nb<6>(GWTF_ARGS);
-    case 7: return launch_nb<7>(GWTF_ARGS);
-    case 8: return launch_nb<8>(GWTF_ARGS);
+    case 1: return launch_nb<1>(nb, a, kk_steps, ex, pipe);
+    case 2: return launch_nb<2>(nb, a, kk_steps, ex, pipe);
+    case 3: return launch_nb<3>(nb, a, kk_steps, ex, pipe);
+    case 4: return launch_nb<4>(nb, a, kk_steps, ex, pipe);
+    case 5: return launch_nb<5>(nb, a, kk_steps, ex, pipe);
+    case 6: return launch_nb<6>(nb, a, kk_steps, ex, pipe);
+    case 7: return launch_nb<7>(nb, a, kk_steps, ex, pipe);
+    case 8: return launch_nb<8>(nb, a, kk_steps, ex, pipe);
     default: return GWTF_E_BADARG;
   }
-#undef GWTF_ARGS
 }
 
-extern "C" int gwtf_stack_forward_flagging(const float* p, const float* packed_w, const float* film, float* out,
-                                           float* logdet, float* ps, float* mus, float* logvars, const int* segments,
-                                           int K, int B, int N, int C, int f, int pattern0, float eps, int mode,
-                                           size_t p_stride_k, size_t out_stride_k, int* worklist, int tune, void* stream) {
-  const Extras ex = {0, 0, nullptr, nullptr, 0, 0, worklist};
-  return stack_dispatch(p, packed_w, film, out, logdet, ps, mus, logvars, segments, K, B, N, C, f, pattern0, eps, mode,
-                        p_stride_k, out_stride_k, ex, tune, stream);
+// see include/gwtf.h
+extern "C" int gwtf_stack_forward(const GwtfStackArgs* args) {
+  const Extras ex = {0, 0, nullptr, nullptr, 0, 0, args ? args->worklist : nullptr};
+  return stack_dispatch(args, ex);
 }
 
-extern "C" int gwtf_stack_forward_multi(const float* p, const float* packed_w, const float* film, float* out,
-                                        float* logdet, float* ps, float* mus, float* logvars, const int* segments,
-                                        int K, int B, int N, int C, int f, int pattern0, float eps, int mode,
-                                        size_t p_stride_k, size_t out_stride_k, int tune, void* stream) {
-  int* worklist = nullptr;
-  const Extras ex = {0, 0, nullptr, nullptr, 0, 0, worklist};
-  return stack_dispatch(p, packed_w, film, out, logdet, ps, mus, logvars, segments, K, B, N, C, f, pattern0, eps, mode,
-                        p_stride_k, out_stride_k, ex, tune, stream);
-}
-
-// One coupling of K stacks in one launch (K-batched train pipeline, gwtf_train.hip): component k reads p + k * p_stride_k,
-// continues logdet + k * out_stride_k, accumulates the next coupling's moments into moments_out + k * moments_stride_k.
-int gwtf_internal_apply_k(const float* p, const float* packed_w, const float* film, float* out, const float* logdet_in,
-                          float* logdet, float* ps, float* mus, float* logvars, float* moments_out, size_t moments_stride_k,
-                          int c, int K, int B, int N, int C, int f, int pattern0, float eps, int mode, size_t p_stride_k,
-                          size_t out_stride_k, int tune, void* stream) {
+// One coupling of K stacks in one launch (K-batched train pipeline, gwtf_train.hip; gwtf_device.h)
+int gwtf_internal_apply_k(const GwtfStackArgs& a, int c, const float* logdet_in, float* moments_out, size_t moments_stride_k) {
   const Extras ex = {c, 1, logdet_in, moments_out, moments_stride_k};
-  return stack_dispatch(p, packed_w, film, out, logdet, ps, mus, logvars, nullptr, K, B, N, C, f, pattern0, eps, mode,
-                        p_stride_k, out_stride_k, ex, tune, stream);
-}
-
-extern "C" int gwtf_stack_forward(const float* p, const float* packed_w, const float* film, float* out, float* logdet,
-                                  float* ps, float* mus, float* logvars, int B, int N, int C, int f, int pattern0,
-                                  float eps, int mode, int tune, void* stream) {
-  return gwtf_stack_forward_multi(p, packed_w, film, out, logdet, ps, mus, logvars, nullptr, 1, B, N, C, f, pattern0, eps,
-                                  mode, 0, 0, tune, stream);
+  return stack_dispatch(&a, ex);
 }
 
 namespace {

@@ -17,10 +17,6 @@ namespace {
 
 using namespace gwtf_dev;
 
-__device__ __forceinline__ float tail_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
-__device__ __forceinline__ float tail_scale(float eps, float logvar) { return __builtin_amdgcn_sqrtf(eps + __expf(logvar)); }
-__device__ __forceinline__ float tail_rscale(float eps, float logvar) { return __builtin_amdgcn_rsqf(eps + __expf(logvar)); }
-
 template <int MB>
 struct XCfg {
   static constexpr int FP = 16 * MB;
@@ -33,12 +29,6 @@ struct XCfg {
 };
 
 constexpr int kLook = 8;      // tiles a workgroup of a re-run launch looks at
-
-struct XJobs {
-  int K;
-  int tiles_cum[GWTF_MAX_COMPONENTS + 1];
-  int begin[GWTF_MAX_COMPONENTS], end[GWTF_MAX_COMPONENTS];
-};
 
 // one elementary coupling on the wave's 16 NB points; L: staged GwtfPackX record followed by the shape's FiLM record
 template <int MB, int NB, int MODE, bool KEEP2>
@@ -125,7 +115,7 @@ __global__ __launch_bounds__(256) void stack_exact_kernel(const float* __restric
                                                           const float* __restrict__ film, float* __restrict__ out,
                                                           float* __restrict__ logdet, float* __restrict__ ps, float* __restrict__ mus,
                                                           float* __restrict__ lvs, int B, int N, int C, int pattern0, float eps, int kk4,
-                                                          const XJobs jobs, size_t p_stride_k, size_t out_stride_k, int only_flagged,
+                                                          const Jobs jobs, size_t p_stride_k, size_t out_stride_k, int only_flagged,
                                                           int* __restrict__ wl) {
   using X = XCfg<MB>;
   constexpr int NBUF = 2 * X::LAYER * 4 <= 160 * 1024 - 512 ? 2 : 1;
@@ -142,7 +132,7 @@ __global__ __launch_bounds__(256) void stack_exact_kernel(const float* __restric
   // workgroup per tile (4096 workgroups with 45 KB of LDS each just to read 128 values and leave), ~3 us this way.
   // re-run mode, phase 1: ALL of this workgroup's tiles are looked at in one round of loads (a tile at a time would be a dependent
   // load + barrier per tile: 8 tiles x ~1 us behind a clean airplane launch), the flagged ones leave a bit in an LDS word
-  // re-run mode WITH A WORK LIST (gwtf_stack_rerun_flagged): the split launch left {shape slot, first point} of every wave that flagged
+  // re-run mode WITH A WORK LIST (GwtfStackArgs.worklist): the split launch left {shape slot, first point} of every wave that flagged
   // a point in wl[2..], their number in wl[0]; a small fixed grid (64 workgroups) walks that list (an empty list -- every clean pass -- is one scalar
   // load per workgroup), checks the listed tile's flags (a tile can be listed by several of its waves: the first re-run clears them) and
   // recomputes it.  More entries than the list holds: every tile is a candidate.  The last workgroup to finish clears the counters.
@@ -165,16 +155,11 @@ __global__ __launch_bounds__(256) void stack_exact_kernel(const float* __restric
       const int bid = (int)blockIdx.x + i * (int)gridDim.x;
       first[i] = 0.f;
       if (bid < jobs.tiles_cum[jobs.K]) {
-        int comp = 0;
-        while (comp + 1 < jobs.K && bid >= jobs.tiles_cum[comp + 1]) ++comp;
-        const int n_begin = jobs.begin[comp], n_end = jobs.end[comp];
-        const int tps = (n_end - n_begin + 64 * NB - 1) / (64 * NB);
-        const int local = bid - jobs.tiles_cum[comp];
-        const int b = local / tps, tile = local - b * tps;
-        const int n = n_begin + tile * 64 * NB + (int)threadIdx.x;          // 64 NB <= 256 points per tile: thread t looks at point t
+        const TileOf t = tile_of<64 * NB>(jobs, bid);
+        const int n = t.n_begin + t.tile * 64 * NB + (int)threadIdx.x;      // 64 NB <= 256 points per tile: thread t looks at point t
         // (the split kernel sets ALL of a flagged point's coordinates and log-dets to NaN, and a non-finite value in any of them flags
         // the point: its first coordinate tells -- 4 B per point to read)
-        if ((int)threadIdx.x < 64 * NB && n < n_end) first[i] = out[comp * out_stride_k + (size_t)b * 3 * N + n];
+        if ((int)threadIdx.x < 64 * NB && n < t.n_end) first[i] = out[t.comp * out_stride_k + (size_t)t.b * 3 * N + n];
       }
     }
     unsigned mine = 0u;
@@ -195,17 +180,14 @@ __global__ __launch_bounds__(256) void stack_exact_kernel(const float* __restric
       const int ltps = (jobs.end[lc] - jobs.begin[lc] + 64 * NB - 1) / (64 * NB);
       bid = jobs.tiles_cum[lc] + lb * ltps + (n_first - jobs.begin[lc]) / (64 * NB);
     }
-    int fc = 0;
-    while (fc + 1 < jobs.K && bid >= jobs.tiles_cum[fc + 1]) ++fc;
-    const int f_begin = jobs.begin[fc], f_end = jobs.end[fc];
-    const int ftps = (f_end - f_begin + 64 * NB - 1) / (64 * NB);
-    const int flocal = bid - jobs.tiles_cum[fc];
-    const int fb = flocal / ftps, ftile = flocal - fb * ftps;
-    const int fn = f_begin + ftile * 64 * NB + (int)threadIdx.x;
+    const TileOf t = tile_of<64 * NB>(jobs, bid);
+    const int fn = t.n_begin + t.tile * 64 * NB + (int)threadIdx.x;
     float first = 0.f;
-    if ((int)threadIdx.x < 64 * NB && fn < f_end) first = out[fc * out_stride_k + (size_t)fb * 3 * N + fn];
+    if ((int)threadIdx.x < 64 * NB && fn < t.n_end) first = out[t.comp * out_stride_k + (size_t)t.b * 3 * N + fn];
     if (!__syncthreads_or(gwtf_nonfinite(first) ? 1 : 0)) continue;
   } else if (only_flagged && !((flagged_mask >> (it & 31)) & 1u)) continue;      // (launch_exact sizes the grid so that it < kLook)
+  // (the same decode as tile_of, written out: through the helper -- by value, by reference or as a lambda -- five of the 64
+  // instantiations change their register count, e.g. <7, 1, INVERSE, lists> 87 -> 95 VGPRs)
   int comp = 0;
   while (comp + 1 < jobs.K && bid >= jobs.tiles_cum[comp + 1]) ++comp;
   const int n_begin = jobs.begin[comp], n_end = jobs.end[comp];
@@ -318,87 +300,48 @@ __global__ __launch_bounds__(256) void stack_exact_kernel(const float* __restric
 }
 
 template <int MB, int NB>
-int launch_exact(const float* p, const float* px, const float* film, float* out, float* logdet, float* ps, float* mus, float* lvs,
-                 int B, int N, int C, int pattern0, float eps, int mode, int kk4, const int* segs, int K, size_t p_stride_k,
-                 size_t out_stride_k, int only_flagged, int* wl, hipStream_t st) {
-  XJobs jobs;
-  jobs.K = K;
-  jobs.tiles_cum[0] = 0;
-  for (int k = 0; k < K; ++k) {
-    jobs.begin[k] = segs ? segs[2 * k] : 0;
-    jobs.end[k] = segs ? segs[2 * k + 1] : N;
-    jobs.tiles_cum[k + 1] = jobs.tiles_cum[k] + B * ((jobs.end[k] - jobs.begin[k] + 64 * NB - 1) / (64 * NB));
-  }
-  if (jobs.tiles_cum[K] == 0) return 0;
-  // re-run launches: a workgroup LOOKS at kLook tiles (their flags are bits of one LDS word)
-  static const int rerun_wgs = [] {
-    const char* e = getenv("GWTF_RERUN_WGS");
-    const int v = e ? atoi(e) : 0;
-    // a clean pass pays for the DISPATCH of these workgroups (45 KB of LDS each) and nothing else: 7.0 / 4.6 / 2.8 / 2.2 us for
-    // 256 / 128 / 64 / 32 of them (airplane launch, inside a hipGraph); 64 keeps a pass with up to 64 flagged tiles in one round
-    return v > 0 ? v : 64;
-  }();
-  const unsigned n_wl = (unsigned)(jobs.tiles_cum[K] < rerun_wgs ? jobs.tiles_cum[K] : rerun_wgs);
-  const dim3 grid(only_flagged ? (wl ? n_wl : (unsigned)((jobs.tiles_cum[K] + kLook - 1) / kLook)) : (unsigned)jobs.tiles_cum[K]), block(256);
-#define GWTF_X(MODE_, LISTS_)                                                                                                    \
-  hipLaunchKernelGGL((stack_exact_kernel<MB, NB, MODE_, LISTS_>), grid, block, 0, st, p, px, film, out, logdet, ps, mus, lvs, B, \
-                     N, C, pattern0, eps, kk4, jobs, p_stride_k, out_stride_k, only_flagged, wl)
-  if (mode == GWTF_MODE_DIRECT) { if (ps) GWTF_X(GWTF_MODE_DIRECT, true); else GWTF_X(GWTF_MODE_DIRECT, false); }
-  else { if (ps) GWTF_X(GWTF_MODE_INVERSE, true); else GWTF_X(GWTF_MODE_INVERSE, false); }
-#undef GWTF_X
+int launch_exact(const GwtfStackArgs& a, int kk4, int only_flagged) {
+  const Jobs jobs = make_jobs(a, 64 * NB);
+  const int tiles = jobs.tiles_cum[a.K];
+  if (tiles == 0) return 0;
+  int* wl = only_flagged ? a.worklist : nullptr;
+  // re-run launches that scan: a workgroup LOOKS at kLook tiles (their flags are bits of one LDS word).  With a work list: a fixed
+  // number of workgroups.  A clean pass pays for their DISPATCH (45 KB of LDS each) and nothing else: 7.0 / 4.6 / 2.8 / 2.2 us for
+  // 256 / 128 / 64 / 32 of them (airplane launch, inside a hipGraph); 64 keeps a pass with up to 64 flagged tiles in one round
+  constexpr int kRerunWgs = 64;
+  const dim3 grid((unsigned)(!only_flagged ? tiles : (wl ? std::min(tiles, kRerunWgs) : (tiles + kLook - 1) / kLook))), block(256);
+  with_mode_lists(a.mode, a.ps != nullptr, [&](auto MODE_, auto LISTS_) {
+    hipLaunchKernelGGL((stack_exact_kernel<MB, NB, decltype(MODE_)::value, decltype(LISTS_)::value>), grid, block, 0,
+                       (hipStream_t)a.stream, a.p, a.weights, a.film, a.out, a.logdet, a.ps, a.mus, a.logvars, a.B, a.N, a.C,
+                       a.pattern0, a.eps, kk4, jobs, a.p_stride_k, a.out_stride_k, only_flagged, wl);
+  });
   return (int)hipGetLastError();
+}
+
+template <int MB>
+int launch_exact_nb(int nb, const GwtfStackArgs& a, int kk4, int only_flagged) {
+  return nb == 1 ? launch_exact<MB, 1>(a, kk4, only_flagged) : launch_exact<MB, 2>(a, kk4, only_flagged);
 }
 
 }  // namespace
 
 // see include/gwtf.h
-static int exact_dispatch(const float* p, const float* packed_x, const float* film, float* out, float* logdet, float* ps,
-                          float* mus, float* logvars, const int* segments, int K, int B, int N, int C, int f,
-                          int pattern0, float eps, int mode, size_t p_stride_k, size_t out_stride_k, int only_flagged, int* wl,
-                          int tune, void* stream) {
-  if (B <= 0 || N <= 0 || C <= 0 || f <= 0 || f > GWTF_MAX_FP || K <= 0 || K > GWTF_MAX_COMPONENTS || !p || !packed_x || !film || !out ||
-      !logdet || (mode != GWTF_MODE_DIRECT && mode != GWTF_MODE_INVERSE) || pattern0 < 0 || pattern0 > 5)
-    return GWTF_E_BADARG;
-  if ((ps || mus || logvars) && !(ps && mus && logvars)) return GWTF_E_BADARG;
-  for (int k = 0; k < K; ++k) {
-    const int b0 = segments ? segments[2 * k] : 0, e0 = segments ? segments[2 * k + 1] : N;
-    if (b0 < 0 || e0 < b0 || e0 > N) return GWTF_E_BADARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int kk4 = (f + 3) / 4;
-  const int forced = (tune & 0xffff) / 16;
+extern "C" int gwtf_stack_forward_exact(const GwtfStackArgs* args, int rerun) {
+  if (!stack_args_ok(args, false) || (rerun != 0 && rerun != 1)) return GWTF_E_BADARG;
+  const GwtfStackArgs& a = *args;
+  const int kk4 = (a.f + 3) / 4;
+  const int forced = (a.tune & 0xffff) / 16;
   // 32 points per wave (16 beyond f = 64: the accumulators of both point blocks would not fit); GWTF_TUNE_POINTS_PER_WAVE overrides
-  const int nb = (forced == 1 || forced == 2) ? forced : (f > 64 ? 1 : 2);
-#define GWTF_XA p, packed_x, film, out, logdet, ps, mus, logvars, B, N, C, pattern0, eps, mode, kk4, segments, K, p_stride_k, out_stride_k, only_flagged, wl, st
-#define GWTF_XM(MB_) return nb == 1 ? launch_exact<MB_, 1>(GWTF_XA) : launch_exact<MB_, 2>(GWTF_XA);
-  switch (gwtf_padded_width(f) / 16) {
-    case 1: GWTF_XM(1)
-    case 2: GWTF_XM(2)
-    case 3: GWTF_XM(3)
-    case 4: GWTF_XM(4)
-    case 5: GWTF_XM(5)
-    case 6: GWTF_XM(6)
-    case 7: GWTF_XM(7)
-    case 8: GWTF_XM(8)
+  const int nb = (forced == 1 || forced == 2) ? forced : (a.f > 64 ? 1 : 2);
+  switch (gwtf_padded_width(a.f) / 16) {
+    case 1: return launch_exact_nb<1>(nb, a, kk4, rerun);
+    case 2: return launch_exact_nb<2>(nb, a, kk4, rerun);
+    case 3: return launch_exact_nb<3>(nb, a, kk4, rerun);
+    case 4: return launch_exact_nb<4>(nb, a, kk4, rerun);
+    case 5: return launch_exact_nb<5>(nb, a, kk4, rerun);
+    case 6: return launch_exact_nb<6>(nb, a, kk4, rerun);
+    case 7: return launch_exact_nb<7>(nb, a, kk4, rerun);
+    case 8: return launch_exact_nb<8>(nb, a, kk4, rerun);
     default: return GWTF_E_BADARG;
   }
-#undef GWTF_XM
-#undef GWTF_XA
-}
-
-extern "C" int gwtf_stack_forward_exact(const float* p, const float* packed_x, const float* film, float* out, float* logdet, float* ps,
-                                        float* mus, float* logvars, const int* segments, int K, int B, int N, int C, int f,
-                                        int pattern0, float eps, int mode, size_t p_stride_k, size_t out_stride_k, int only_flagged,
-                                        int tune, void* stream) {
-  return exact_dispatch(p, packed_x, film, out, logdet, ps, mus, logvars, segments, K, B, N, C, f, pattern0, eps, mode, p_stride_k,
-                        out_stride_k, only_flagged, nullptr, tune, stream);
-}
-
-extern "C" int gwtf_stack_rerun_flagged(const float* p, const float* packed_x, const float* film, float* out, float* logdet, float* ps,
-                                        float* mus, float* logvars, const int* segments, int K, int B, int N, int C, int f,
-                                        int pattern0, float eps, int mode, size_t p_stride_k, size_t out_stride_k, int* worklist,
-                                        int tune, void* stream) {
-  if (!worklist) return GWTF_E_BADARG;
-  return exact_dispatch(p, packed_x, film, out, logdet, ps, mus, logvars, segments, K, B, N, C, f, pattern0, eps, mode, p_stride_k,
-                        out_stride_k, 1, worklist, tune, stream);
 }

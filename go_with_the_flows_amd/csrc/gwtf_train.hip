@@ -189,25 +189,6 @@ int train_moments(const float* p, float* moments, int B, int N, void* stream) {
 
 }  // namespace
 
-// internal K-batched pieces defined in gwtf_stack.hip / gwtf_bwd.hip
-int gwtf_internal_stats_k(const float* p, const float* packed_w_c, float* ystats, int K, int B, int N, int f, int pattern,
-                          size_t p_sk, size_t pw_sk, size_t ys_sk, int tune, void* stream);
-int gwtf_internal_apply_k(const float* p, const float* packed_w, const float* film, float* out, const float* logdet_in,
-                          float* logdet, float* ps, float* mus, float* logvars, float* moments_out, size_t moments_stride_k,
-                          int c, int K, int B, int N, int C, int f, int pattern0, float eps, int mode, size_t p_stride_k,
-                          size_t out_stride_k, int tune, void* stream);
-int gwtf_internal_light_backward_k(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
-                                   const float* film, float* g_film, float* g_bias, int c, int K, int B, int N, int f,
-                                   int pattern0, float eps, int mode, const GwtfKS& ks, const float* g_ps_c,
-                                   const float* g_lvs_c, const GwtfCombine& cmb, void* stream);
-int gwtf_internal_merged_backward_k(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
-                                    const float* packed_b_c, const float* film, const float* g_stats, float* g_in, float* dw1_ws,
-                                    float* g_sd0, int c, int K, int B, int N, int f, int pattern0, float eps, int mode,
-                                    const GwtfKS& ks, const float* g_ps_c, const float* g_lvs_c, const GwtfCombine& cmb,
-                                    void* stream);
-int gwtf_internal_dw1_reduce_k(float* workspace, int passes, float* dW1, size_t branch_stride, int f, int B, int N, int K,
-                               size_t ws_sk, size_t out_sk, void* stream);
-
 // =====================================================================================================================
 // Backward of the folds (train mode): each fold's backward is ONE small launch of the pipeline's backward phases.
 // =====================================================================================================================
@@ -716,9 +697,13 @@ extern "C" int gwtf_mtrain_phase(const GwtfTrainCtx* t, int phase, int step) {
                            t->n_total, t->film_raw, t->film_rec, t->bn_batch + (size_t)c * d.BS, c, C, f, G, FP, ks);
       float* nxt = t->xbuf + (size_t)(step & 1) * K * d.XS;
       float* mom_next = step + 1 < C ? t->moments + (size_t)(step + 1) * K * d.MS : nullptr;
-      int rc = gwtf_internal_apply_k(cur, t->packed_w, t->film_rec, nxt, step > 0 ? t->logdet : nullptr, t->logdet, t->ps, t->mus,
-                                     t->logvars, mom_next, d.MS, c, K, B, N, C, f, t->pattern0, t->eps, t->mode, ks.x, d.XS, t->tune,
-                                     t->stream);
+      GwtfStackArgs a = {};
+      a.p = cur; a.weights = t->packed_w; a.film = t->film_rec; a.out = nxt; a.logdet = t->logdet;
+      a.ps = t->ps; a.mus = t->mus; a.logvars = t->logvars;
+      a.p_stride_k = ks.x; a.out_stride_k = d.XS;
+      a.K = K; a.B = B; a.N = N; a.C = C; a.f = f; a.pattern0 = t->pattern0; a.mode = t->mode; a.tune = t->tune;
+      a.eps = t->eps; a.stream = t->stream;
+      int rc = gwtf_internal_apply_k(a, c, step > 0 ? t->logdet : nullptr, mom_next, d.MS);
       if (!rc && mom_next && t->mom_c) compact(mom_next, d.MS, t->mom_c + (size_t)(step + 1) * K * 16, K, 16, st);
       return rc ? rc : (int)hipGetLastError();
     }

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define GWTF_ABI_VERSION 8
+#define GWTF_ABI_VERSION 9
 #define GWTF_E_BADARG 10001   /* shape / mode / width outside what the kernels support */
 #define GWTF_E_UNSUPPORTED 10002   /* a layer-width list no kernel instantiation was built for */
 #define GWTF_MODE_DIRECT 0    /* sampling direction  base -> data (reference models.py:202) */
@@ -53,18 +53,16 @@ size_t gwtf_film_out_floats(int f);                   /* FiLM output per (shape,
  * f to FP and lays the weights out in MFMA-fragment / coalesced order.
  * Replaces the per-call parameter reads of nn.BatchNorm1d + SharedDot in
  * lib/networks/flows.py:25-50,60-85 (module construction) as consumed by :95-107.
- *   raw          [C][gwtf_raw_coupling_floats]   parameters + running statistics, direct order
+ *   raw          [K*Cper][gwtf_raw_coupling_floats]   parameters + running statistics, direct order
  *   pattern0     warp pattern index of coupling 0 (the raw record stores sd0.weight as the module does, [f][k] with
  *                k = 1 or 2 kept coordinates: the packer needs each coupling's k)
- *   packed_w     [C][gwtf_packed_w_coupling_floats]
- *   packed_film  [C][gwtf_packed_film_coupling_floats]
+ *   packed_w     [K*Cper][gwtf_packed_w_coupling_floats]
+ *   packed_film  [K*Cper][gwtf_packed_film_coupling_floats]
  *   training     0: fold running statistics (model.eval()); 1: the train pipeline's packing (model.train()) -- packed_w only, in
  *                train form (sd1 un-scaled, sd0 records left to the pipeline's fold0); packed_film may be NULL: the pipeline's
  *                FiLM heads read the raw arena in place (gwtf_film_heads_forward). */
-int gwtf_pack_weights(const float* raw, float* packed_w, float* packed_film,
-                      int C, int f, int G, int pattern0, int training, void* stream);
-/* The same for K concatenated stacks of Cper couplings each (the components of a mixture): raw [K][Cper][...], every stack
- * starts again at warp pattern `pattern0`. */
+/* K concatenated stacks of Cper couplings each (the components of a mixture; K = 1: one stack, C = Cper): raw [K][Cper][...],
+ * every stack starts again at warp pattern `pattern0`. */
 int gwtf_pack_weights_k(const float* raw, float* packed_w, float* packed_film,
                         int K, int Cper, int f, int G, int pattern0, int training, void* stream);
 
@@ -81,65 +79,58 @@ int gwtf_film_forward(const float* g, const float* packed_film, float* film_out,
 /* Fused coupling stack: all C elementary couplings applied to every point, with the log-det
  * accumulation.  Replaces LocalCondRNVPDecoder.forward (lib/networks/decoders.py:61-79) ->
  * CondRealNVPFlow3DTriple.forward (flows.py:150-160) -> CondRealNVPFlow3D.forward (flows.py:95-117)
- * and the `sum(logvars)` of lib/networks/losses.py:14,115.
- *   p        [B][3][N]   input coordinates (data for INVERSE, base samples for DIRECT)
- *   out      [B][3][N]   coordinates after the whole stack (ps[0] for INVERSE, ps[-1] for DIRECT)
- *   logdet   [B][3][N]   sum over the C couplings of logvar (per coordinate; the reference's
- *                        definition of the log-det, NOT including the base logvar0)
- *   ps, mus, logvars     optional (all three NULL, or all three non-NULL) [C][B][3][N]: the
- *                        per-coupling lists the reference returns, slot j = direct-order coupling j
- *   pattern0 warp pattern index of coupling 0 (0 for a decoder / pattern-0 Triple; see gwtf_layout.h)
- *   mode     GWTF_MODE_DIRECT / GWTF_MODE_INVERSE */
-int gwtf_stack_forward(const float* p, const float* packed_w, const float* film,
-                       float* out, float* logdet, float* ps, float* mus, float* logvars,
-                       int B, int N, int C, int f, int pattern0, float eps, int mode, int tune, void* stream);
-
-/* K flow components in ONE launch (the loop over `self.pc_decoder[i]` in Flow_Mixture_Model.decode,
- * lib/networks/flow_mixture.py:163-166).  Component k applies its own C-coupling stack to the points
- * [segments[2k], segments[2k+1]) of every shape (segments == NULL: every component takes all N points).
- *   packed_w [K][C][...]            the K components' packed weights, concatenated
- *   film     [B][K*C][...]          gwtf_film_forward run once on the concatenated FiLM weights with C' = K*C
- *   p        base + k*p_stride_k    (floats; 0: all components read the same clouds)
- *   out, logdet base + k*out_stride_k  (floats; B*3*N for the density path -> [K][B][3][N], the layout
- *                                   gwtf_mixture_nll reads; 0 for the sampling path where the segments partition N)
- *   ps, mus, logvars                optional lists, [K][C][B][3][N] when out_stride_k != 0 else [C][B][3][N]
- *   segments                        HOST array of 2K ints, or NULL;  K <= 64 */
-int gwtf_stack_forward_multi(const float* p, const float* packed_w, const float* film,
-                             float* out, float* logdet, float* ps, float* mus, float* logvars,
-                             const int* segments, int K, int B, int N, int C, int f, int pattern0, float eps,
-                             int mode, size_t p_stride_k, size_t out_stride_k, int tune, void* stream);
+ * and the `sum(logvars)` of lib/networks/losses.py:14,115 -- for K flow components in ONE launch (the loop over
+ * `self.pc_decoder[i]` in Flow_Mixture_Model.decode, lib/networks/flow_mixture.py:163-166; K = 1: one decoder).
+ * Everything a stack launch takes is one record, read by both entry points below. */
+#define GWTF_WORKLIST_CAP 2048
+#define GWTF_WORKLIST_INTS (2 + 2 * GWTF_WORKLIST_CAP)
+typedef struct GwtfStackArgs {
+  const float* p;            /* [B][3][N]  input coordinates (data for INVERSE, base samples for DIRECT); component k reads p + k*p_stride_k */
+  const float* weights;      /* [K][C][...]  the K components' records, concatenated: packed_w (gwtf_pack_weights_k) for gwtf_stack_forward,
+                              * packed_x (gwtf_pack_weights_exact of the same raw arena, [K*C][gwtf_packed_x_coupling_floats]) for
+                              * gwtf_stack_forward_exact */
+  const float* film;         /* [B][K*C][...]  gwtf_film_forward run once on the concatenated FiLM weights with C' = K*C; both entry
+                              * points read the SAME records */
+  float* out;                /* [B][3][N]  coordinates after the whole stack (ps[0] for INVERSE, ps[-1] for DIRECT); component k writes
+                              * out + k*out_stride_k */
+  float* logdet;             /* [B][3][N]  sum over the C couplings of logvar (per coordinate; the reference's definition of the log-det,
+                              * NOT including the base logvar0); component k writes logdet + k*out_stride_k */
+  float* ps;                 /* optional (all three NULL, or all three non-NULL): the per-coupling lists the reference returns, slot j =
+                              * direct-order coupling j; [K][C][B][3][N] when out_stride_k != 0 else [C][B][3][N] */
+  float* mus;
+  float* logvars;
+  const int* segments;       /* HOST array of 2K ints, or NULL: component k takes the points [segments[2k], segments[2k+1]) of every shape
+                              * (NULL: every component takes all N points);  K <= 64 */
+  int* worklist;             /* NULL, or GWTF_WORKLIST_INTS ints of device memory, zero before the FIRST use, owned by one stream at a time
+                              * (the pair below keeps it zero between uses): the flagged-tile list between a split launch and its re-run */
+  size_t p_stride_k;         /* floats; 0: all components read the same clouds */
+  size_t out_stride_k;       /* floats; B*3*N for the density path -> [K][B][3][N], the layout gwtf_mixture_nll reads; 0 for the sampling
+                              * path where the segments partition N */
+  int K, B, N, C, f;
+  int pattern0;              /* warp pattern index of coupling 0 (0 for a decoder / pattern-0 Triple; see gwtf_layout.h) */
+  int mode;                  /* GWTF_MODE_DIRECT / GWTF_MODE_INVERSE */
+  int tune;                  /* GWTF_TUNE_* word; gwtf_stack_forward_exact reads GWTF_TUNE_POINTS_PER_WAVE(16 | 32) only */
+  float eps;                 /* the coupling's `eps` buffer (reference flows.py:21, 1e-6) */
+  void* stream;
+} GwtfStackArgs;
+/* The split-f16 body (csrc/gwtf_stack.hip).  A point whose coordinate left the f16-safe range (|x| > 3e4) is flagged with NaN; with
+ * worklist != NULL a wave that flags a point also appends {component * B + shape, first point} to worklist[2 + 2 i], i = atomic
+ * increment of worklist[0]. */
+int gwtf_stack_forward(const GwtfStackArgs* args);
 /* The same stack with the f x f contraction on the EXACT-fp32 matrix instruction (v_mfma_f32_16x16x4_f32, unsplit operands):
  * the arithmetic of the reference's torch.matmul in SharedDot (lib/networks/layers.py:40-45 as called by flows.py:95-117), no
- * operand range limit (csrc/gwtf_stack_exact.hip).  packed_x: gwtf_pack_weights_exact of the same raw arena
- * [K*C][gwtf_packed_x_coupling_floats]; film: the SAME FiLM records gwtf_film_forward wrote for the split kernel.
- *   only_flagged = 0: every tile is computed (on-device A/B of the split-f16 contraction; the fp32-MFMA comparison point).
- *   only_flagged = 1: RE-RUN after gwtf_stack_forward[_multi] with the same arguments -- a workgroup reads its tile's out / logdet,
- *                     returns at once if they are all finite, and otherwise recomputes the tile (all list slots included): points the
- *                     split kernel flagged with NaN because a coordinate left the f16-safe range (|x| > 3e4) come back with the
- *                     reference's finite fp32 values; genuinely non-finite inputs / parameters stay NaN.
- * ps, mus, logvars: all three or none.  tune: GWTF_TUNE_POINTS_PER_WAVE(16 | 32) only. */
+ * operand range limit (csrc/gwtf_stack_exact.hip).
+ *   rerun = 0: every tile is computed (on-device A/B of the split-f16 contraction; the fp32-MFMA comparison point).
+ *   rerun = 1: RE-RUN after gwtf_stack_forward with the same record (weights = packed_x) -- tiles whose out / logdet are all finite are
+ *              left alone, the others are recomputed (all list slots included): points the split kernel flagged with NaN come back
+ *              with the reference's finite fp32 values; genuinely non-finite inputs / parameters stay NaN.
+ *              worklist != NULL: the launch walks the list the split launch left (all tiles when worklist[0] > GWTF_WORKLIST_CAP) and
+ *              its last workgroup clears worklist[0..1] -- the re-run behind a clean pass costs the dispatch of 64 idle workgroups
+ *              (2.8 us per forward pass of the airplane config).  worklist == NULL: a scan of every tile's flags (7 us). */
 size_t gwtf_packed_x_coupling_floats(int f);
 int gwtf_pack_weights_exact(const float* raw, const float* packed_film /*eval packing of the same arena: its range exponents*/,
                             float* packed_x, int K, int Cper, int f, int G, int pattern0, void* stream);
-int gwtf_stack_forward_exact(const float* p, const float* packed_x, const float* film, float* out, float* logdet, float* ps,
-                             float* mus, float* logvars, const int* segments, int K, int B, int N, int C, int f, int pattern0,
-                             float eps, int mode, size_t p_stride_k, size_t out_stride_k, int only_flagged, int tune, void* stream);
-/* The same pair with a WORK LIST, so that the re-run launch behind a clean pass costs the dispatch of 64 idle workgroups instead of a
- * scan of every tile's flags (7 us -> 2.8 per forward pass of the airplane config):
- *   gwtf_stack_forward_flagging  = gwtf_stack_forward_multi; a wave that flags a point appends {component * B + shape, first point}
- *                                  to worklist[2 + 2 i], i = atomic increment of worklist[0]
- *   gwtf_stack_rerun_flagged     = gwtf_stack_forward_exact(only_flagged = 1) over the listed tiles (all tiles when worklist[0] >
- *                                  GWTF_WORKLIST_CAP); its last workgroup clears worklist[0..1]
- * worklist: GWTF_WORKLIST_INTS ints of device memory, zero before the FIRST use, owned by one stream at a time (the pair keeps it
- * zero between uses). */
-#define GWTF_WORKLIST_CAP 2048
-#define GWTF_WORKLIST_INTS (2 + 2 * GWTF_WORKLIST_CAP)
-int gwtf_stack_forward_flagging(const float* p, const float* packed_w, const float* film, float* out, float* logdet, float* ps,
-                                float* mus, float* logvars, const int* segments, int K, int B, int N, int C, int f, int pattern0,
-                                float eps, int mode, size_t p_stride_k, size_t out_stride_k, int* worklist, int tune, void* stream);
-int gwtf_stack_rerun_flagged(const float* p, const float* packed_x, const float* film, float* out, float* logdet, float* ps, float* mus,
-                             float* logvars, const int* segments, int K, int B, int N, int C, int f, int pattern0, float eps, int mode,
-                             size_t p_stride_k, size_t out_stride_k, int* worklist, int tune, void* stream);
+int gwtf_stack_forward_exact(const GwtfStackArgs* args, int rerun);
 /* Latent-space loss terms of the training step and their combination with the point NLL (reference lib/networks/losses.py:24-33
  * GaussianFlowNLL, :36-41 GaussianEntropy, :159-170 Flow_Mixture_Loss.forward), one launch each way (csrc/gwtf_latent.hip):
  *   nll [B] per-shape point NLL (gwtf_mixture_nll); z [B][G] = g_prior_samples[0]; mu0, lv0 [G] = the base Gaussian of the prior flow;
@@ -222,7 +213,7 @@ typedef struct GwtfTrainCtx {
   double n_total;            /* points the statistics cover: B*N summed over all ranks */
   const float* p;            /* [B][3][N]            input clouds, shared by the K components */
   const float* raw;          /* [K][C][raw record]   parameters + buffers (gwtf_layout.h GwtfRaw) */
-  float* packed_w;           /* [K][C][packed_w]     from gwtf_pack_weights(training=1); fold0 fills the sd0 records */
+  float* packed_w;           /* [K][C][packed_w]     from gwtf_pack_weights_k(training=1); fold0 fills the sd0 records */
   float* packed_b;           /* [K][C][packed_b]     from gwtf_pack_w1t; fold0 fills the sd0 sections; NULL: no backward */
   const float* film_raw;     /* [B][K*C][2][2][FP]   raw FiLM {a, b} per shape (batch-statistic FiLM BatchNorm applied) */
   float* film_rec;           /* [B][K*C][gwtf_film_out_floats]  written by fold1, read by apply and the backward */

@@ -58,6 +58,31 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert b'bad argument' in L.gwtf_error_string(10001)
 
 
+def _c_struct_fields(header, name):
+    """[(field, kind)] of `typedef struct <name> { ... } <name>;` in declaration order; kind: pointer / int / float / double / size_t."""
+    body = re.search(r'typedef struct %s \{(.*?)\} %s;' % (name, name), header, re.S).group(1)
+    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(';'))):
+        ctype, names = re.fullmatch(r'((?:const\s+)?(?:unsigned\s+)?\w+(?:\s*\*)?)\s*(\w+(?:\s*,\s*\w+)*)', decl).groups()
+        kind = 'pointer' if '*' in ctype else ctype
+        assert kind in ('pointer', 'int', 'float', 'double', 'size_t'), decl
+        fields += [(n.strip(), kind) for n in names.split(',')]
+    return fields
+
+
+def test_ctypes_records_follow_the_header_field_for_field():
+    """_lib.StackArgs / _lib.TrainCtx are hand-written mirrors of GwtfStackArgs / GwtfTrainCtx: same names, same order, same kind of
+    C type -- a transposed or missing field would bind and load without complaint and shift every field behind it."""
+    header = open(os.path.join(ROOT, 'include', 'gwtf.h')).read()
+    kinds = {ctypes.c_int: 'int', ctypes.c_float: 'float', ctypes.c_double: 'double', ctypes.c_size_t: 'size_t',
+             ctypes.c_void_p: 'pointer', ctypes.POINTER(ctypes.c_int): 'pointer'}
+    for c_name, mirror in (('GwtfStackArgs', _lib.StackArgs), ('GwtfTrainCtx', _lib.TrainCtx)):
+        declared = _c_struct_fields(header, c_name)
+        assert len(declared) > 20, c_name
+        assert [(n, kinds[t]) for n, t in mirror._fields_] == declared, c_name
+
+
 def test_buffer_sizes_and_raw_arena_layout():
     L = _lib.lib()
     for f, G in [(8, 16), (19, 128), (33, 512), (37, 128), (64, 128)]:
@@ -87,8 +112,10 @@ def test_no_cpu_fallback_and_bad_arguments():
         gw.LocalCondRNVPDecoder(1, 129, 16).engine()
     # bad arguments are rejected by the library itself before anything is launched
     L = _lib.lib()
-    assert L.gwtf_stack_forward(None, None, None, None, None, None, None, None, 1, 1, 1, 8, 0, 1e-6, 1, 0, None) == 10001
-    assert L.gwtf_pack_weights(None, None, None, 1, 8, 16, 0, 0, None) == 10001
+    null_record = _lib.StackArgs(K=1, B=1, N=1, C=1, f=8, pattern0=0, mode=1, tune=0, eps=1e-6)     # valid shape, NULL pointers
+    assert L.gwtf_stack_forward(ctypes.addressof(null_record)) == 10001
+    assert L.gwtf_stack_forward(None) == 10001                                                      # a NULL record
+    assert L.gwtf_pack_weights_k(None, None, None, 1, 1, 8, 16, 0, 0, None) == 10001
     assert L.gwtf_mixture_nll(None, None, None, None, None, None, None, 65, 1, 1, None) == 10001
 
 
