@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GWTF_LIB') or os.path.join(_HERE, 'libgwtf_hip.so')      # GWTF_LIB: an A/B build (tools/ab_build.sh)
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 MODE_DIRECT, MODE_INVERSE = 0, 1
 STAT_REPLICAS = 64   # GWTF_STAT_REPLICAS in csrc/gwtf_layout.h
@@ -56,6 +56,8 @@ _SIGNATURES = {
     'gwtf_nn_distance_grad': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 3 + [_c_fp]),
     'gwtf_approx_match': (ctypes.c_int, [_c_fp] * 4 + [ctypes.c_int] * 3 + [_c_fp]),
     'gwtf_emd_cost': (ctypes.c_int, [_c_fp] * 4 + [ctypes.c_int] * 3 + [_c_fp]),
+    'gwtf_emd_cost_pairs': (ctypes.c_int, [_c_fp] * 4 + [ctypes.c_int] * 6 + [_c_fp]),
+    'gwtf_chamfer_directed': (ctypes.c_int, [_c_fp] * 4 + [ctypes.POINTER(ctypes.c_float)] + [ctypes.c_int] * 5 + [_c_fp]),
     'gwtf_match_cost': (ctypes.c_int, [_c_fp] * 4 + [ctypes.c_int] * 3 + [_c_fp]),
     'gwtf_match_cost_grad': (ctypes.c_int, [_c_fp] * 5 + [ctypes.c_int] * 3 + [_c_fp]),
     'gwtf_encoder_raw_floats': (ctypes.c_size_t, [_c_fp, ctypes.c_int]),

@@ -12,6 +12,16 @@ namespace {
 
 constexpr int kTile = 1024;   // points of the "other" set staged in LDS per step (16 KiB as float4)
 
+// |b - a|^2 as every Chamfer kernel of this file evaluates it: b - a per coordinate, (dx dx + dy dy) + dz dz, no FMA (the library is
+// built with -ffp-contract=off).  T = float, or a 2-vector of floats (two query points per packed instruction): elementwise, so
+// the bits of a lane do not depend on T.
+typedef float float2v __attribute__((ext_vector_type(2)));
+template <class T>
+__device__ inline T sqdist3(T bx, T by, T bz, T ax, T ay, T az) {
+  const T dx = bx - ax, dy = by - ay, dz = bz - az;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
 // dist[i][j] = min_k |a_j - b_k|^2, idx = first minimiser (reference nndistance.cu:2-124: strict '<' inside a tile,
 // strict '>' across tiles).  grid = (query tiles, batch, 2 directions); 256 threads x 2 query points each.
 __global__ __launch_bounds__(256) void nnd_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2,
@@ -45,16 +55,123 @@ __global__ __launch_bounds__(256) void nnd_kernel(const float* __restrict__ xyz1
 #pragma unroll 4
     for (int k = 0; k < cnt; ++k) {
       const float4 q = buf[k];   // same address in every lane: LDS broadcast
-      const float dx0 = q.x - ax0, dy0 = q.y - ay0, dz0 = q.z - az0;
-      const float dx1 = q.x - ax1, dy1 = q.y - ay1, dz1 = q.z - az1;
-      const float d0 = dx0 * dx0 + dy0 * dy0 + dz0 * dz0;
-      const float d1 = dx1 * dx1 + dy1 * dy1 + dz1 * dz1;
+      const float d0 = sqdist3(q.x, q.y, q.z, ax0, ay0, az0);
+      const float d1 = sqdist3(q.x, q.y, q.z, ax1, ay1, az1);
       if (d0 < best0) { best0 = d0; bi0 = k0 + k; }
       if (d1 < best1) { best1 = d1; bi1 = k0 + k; }
     }
   }
   if (v0) { dist[(size_t)i * na + j0] = best0; idx[(size_t)i * na + j0] = bi0; }
   if (v1) { dist[(size_t)i * na + j1] = best1; idx[(size_t)i * na + j1] = bi1; }
+}
+
+// Directed Chamfer reduction over ALL ordered pairs of two sets of clouds: sum[i][j] = sum_{a in q_i} min_{b in t_j} |a - b|^2 and
+// cnt[h][i][j] = #{a in q_i : min < thr[h]} (float32 compare).  The per-point minimum is nnd_kernel's dist1 bit for bit (same
+// sqdist3, min instead of compare-and-select: no index is kept).  One workgroup = one query cloud x one GROUP of kCdGroup target
+// clouds: the query points sit in registers (256 threads x 8 points = 2048 per chunk, longer clouds in chunks of that), the
+// targets stream through the LDS tile, so one broadcast LDS read serves 8 evaluations and the query load is paid once per group.
+// Reductions are per pair and inside the workgroup -- lane (points in order), wave (shuffle tree), waves in order, chunks in
+// order -- so a result does not depend on the launch; no float atomics.  grid.x = nq * ceil(nt / kCdGroup).
+constexpr int kCdGroup = 8;      // target clouds per workgroup
+constexpr int kCdPts = 8;        // query points per thread
+constexpr int kCdChunk = 256 * kCdPts;
+constexpr int kCdMaxThr = 8;
+struct CdThr { float v[kCdMaxThr]; };
+
+__global__ __launch_bounds__(256) void chamfer_directed_kernel(const float* __restrict__ q, const float* __restrict__ t,
+                                                               float* __restrict__ sum, int* __restrict__ cnt, CdThr thr,
+                                                               int n_thr, int nq, int nt, int n, int m) {
+  __shared__ float4 buf[kTile];
+  __shared__ float wsum[4];
+  __shared__ int wcnt[4][kCdMaxThr];
+  __shared__ float acc_sum[kCdGroup];
+  __shared__ int acc_cnt[kCdGroup][kCdMaxThr];
+  const int groups = (nt + kCdGroup - 1) / kCdGroup;
+  const int i = blockIdx.x / groups, j0 = (blockIdx.x % groups) * kCdGroup;
+  const int nj = min(kCdGroup, nt - j0);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < kCdGroup) {
+    acc_sum[tid] = 0.f;
+#pragma unroll
+    for (int h = 0; h < kCdMaxThr; ++h) acc_cnt[tid][h] = 0;
+  }
+  const float* Q = q + (size_t)i * n * 3;
+  for (int c0 = 0; c0 < n; c0 += kCdChunk) {
+    float2v ax[kCdPts / 2], ay[kCdPts / 2], az[kCdPts / 2];
+#pragma unroll
+    for (int p = 0; p < kCdPts; ++p) {     // point c0 + p * 256 + tid: consecutive lanes read consecutive points
+      const int k = c0 + p * 256 + tid;
+      const bool v = k < n;
+      ax[p / 2][p % 2] = v ? Q[(size_t)k * 3 + 0] : 0.f;
+      ay[p / 2][p % 2] = v ? Q[(size_t)k * 3 + 1] : 0.f;
+      az[p / 2][p % 2] = v ? Q[(size_t)k * 3 + 2] : 0.f;
+    }
+    for (int jj = 0; jj < nj; ++jj) {
+      const float* T = t + (size_t)(j0 + jj) * m * 3;
+      float2v best[kCdPts / 2];
+#pragma unroll
+      for (int p = 0; p < kCdPts / 2; ++p) best[p] = float2v{3.4e38f, 3.4e38f};
+      for (int k0 = 0; k0 < m; k0 += kTile) {
+        const int cn = min(kTile, m - k0);
+        __syncthreads();
+        for (int s = tid; s < cn; s += 256) {
+          const float* b = T + (size_t)(k0 + s) * 3;
+          buf[s] = make_float4(b[0], b[1], b[2], 0.f);
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int k = 0; k < cn; ++k) {
+          const float4 b = buf[k];   // same address in every lane: LDS broadcast
+          const float2v bx = {b.x, b.x}, by = {b.y, b.y}, bz = {b.z, b.z};
+#pragma unroll
+          for (int p = 0; p < kCdPts / 2; ++p) {
+            const float2v d = sqdist3(bx, by, bz, ax[p], ay[p], az[p]);
+            best[p] = float2v{fminf(best[p][0], d[0]), fminf(best[p][1], d[1])};
+          }
+        }
+      }
+      // this chunk's share of pair (i, j0 + jj)
+      float s = 0.f;
+      int c[kCdMaxThr];
+#pragma unroll
+      for (int h = 0; h < kCdMaxThr; ++h) c[h] = 0;
+#pragma unroll
+      for (int p = 0; p < kCdPts; ++p) {
+        const float d = best[p / 2][p % 2];
+        if (c0 + p * 256 + tid < n) {
+          s += d;
+#pragma unroll
+          for (int h = 0; h < kCdMaxThr; ++h) c[h] += (h < n_thr && d < thr.v[h]) ? 1 : 0;
+        }
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+#pragma unroll
+      for (int h = 0; h < kCdMaxThr; ++h) {
+        if (h < n_thr) {             // uniform
+#pragma unroll
+          for (int off = 32; off > 0; off >>= 1) c[h] += __shfl_down(c[h], off);
+        }
+      }
+      if (lane == 0) {
+        wsum[wave] = s;
+#pragma unroll
+        for (int h = 0; h < kCdMaxThr; ++h) wcnt[wave][h] = c[h];
+      }
+      __syncthreads();
+      if (tid == 0) {
+        acc_sum[jj] += ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+#pragma unroll
+        for (int h = 0; h < kCdMaxThr; ++h) acc_cnt[jj][h] += ((wcnt[0][h] + wcnt[1][h]) + wcnt[2][h]) + wcnt[3][h];
+      }
+      // the next tile's first barrier orders thread 0's reads of wsum / wcnt before they are written again
+    }
+  }
+  __syncthreads();
+  if (tid < nj) {
+    sum[(size_t)i * nt + j0 + tid] = acc_sum[tid];
+    for (int h = 0; h < n_thr; ++h) cnt[((size_t)h * nq + i) * nt + j0 + tid] = acc_cnt[tid][h];
+  }
 }
 
 // reference nndistance.cu:129-148: grad_a[j] += 2 g_j (a_j - b_idx[j]); grad_b[idx[j]] -= the same.  z = direction.
@@ -93,16 +210,21 @@ __global__ __launch_bounds__(256) void nnd_grad_kernel(const float* __restrict__
 // batch of 64 pairs of 2048 points puts 512 workgroups on the 256 CUs, and the stream order is the barrier between
 // sweeps.  exp(level d) is evaluated as exp2((level log2 e) d) with the bare v_exp_f32 (results below 2^-126 flush to 0).
 // temp: [b][2(n+m)] = remainL[n] | remainR[m] | ratioL[n] | ratioR[m]
+// Pair index i (blockIdx.y) owns temp / match / out slot i.  GRID = false: it is also the cloud index on both sides (cloud i of xyz1
+// against cloud i of xyz2).  GRID = true (gwtf_emd_cost_pairs): the pairs are a rows x nb grid, A-cloud row0 + i / nb of xyz1 against
+// B-cloud i % nb of xyz2 -- no expanded copy of either set.
 constexpr int kEmdThreads = 256;
 constexpr int kEmdTile = 1024;
 
 struct EmdPair {
   const float* A; const float* Bp; float* M; float* remainL; float* remainR; float* ratioL; float* ratioR;
 };
-__device__ inline EmdPair emd_pair(const float* xyz1, const float* xyz2, float* match, float* temp, int i, int n, int m) {
+template <bool GRID>
+__device__ inline EmdPair emd_pair(const float* xyz1, const float* xyz2, float* match, float* temp, int i, int n, int m, int nb,
+                                   int row0) {
   EmdPair p;
-  p.A = xyz1 + (size_t)i * n * 3;
-  p.Bp = xyz2 + (size_t)i * m * 3;
+  p.A = xyz1 + (size_t)(GRID ? row0 + i / nb : i) * n * 3;
+  p.Bp = xyz2 + (size_t)(GRID ? i % nb : i) * m * 3;
   p.M = match + (size_t)i * n * m;
   p.remainL = temp + (size_t)i * (n + m) * 2;
   p.remainR = p.remainL + n;
@@ -169,10 +291,12 @@ __device__ inline float emd_sweep(const float* __restrict__ other, const float* 
   return acc;
 }
 
+template <bool GRID>
 __global__ __launch_bounds__(kEmdThreads) void emd_left_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2,
-                                                               float* __restrict__ temp, int n, int m, float lvl2) {
+                                                               float* __restrict__ temp, int n, int m, float lvl2, int nb,
+                                                               int row0) {
   __shared__ float4 buf[kEmdTile];
-  const EmdPair P = emd_pair(xyz1, xyz2, nullptr, temp, blockIdx.y, n, m);
+  const EmdPair P = emd_pair<GRID>(xyz1, xyz2, nullptr, temp, blockIdx.y, n, m, nb, row0);
   const int k = blockIdx.x * kEmdThreads + threadIdx.x;
   const bool v = k < n;
   const float x1 = v ? P.A[k * 3] : 0.f, y1 = v ? P.A[k * 3 + 1] : 0.f, z1 = v ? P.A[k * 3 + 2] : 0.f;
@@ -181,10 +305,12 @@ __global__ __launch_bounds__(kEmdThreads) void emd_left_kernel(const float* __re
   if (v) P.ratioL[k] = P.remainL[k] / (1e-9f + s);
 }
 
+template <bool GRID>
 __global__ __launch_bounds__(kEmdThreads) void emd_right_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2,
-                                                                float* __restrict__ temp, int n, int m, float lvl2) {
+                                                                float* __restrict__ temp, int n, int m, float lvl2, int nb,
+                                                                int row0) {
   __shared__ float4 buf[kEmdTile];
-  const EmdPair P = emd_pair(xyz1, xyz2, nullptr, temp, blockIdx.y, n, m);
+  const EmdPair P = emd_pair<GRID>(xyz1, xyz2, nullptr, temp, blockIdx.y, n, m, nb, row0);
   const int l = blockIdx.x * kEmdThreads + threadIdx.x;
   const bool v = l < m;
   const float x2 = v ? P.Bp[l * 3] : 0.f, y2 = v ? P.Bp[l * 3 + 1] : 0.f, z2 = v ? P.Bp[l * 3 + 2] : 0.f;
@@ -198,13 +324,14 @@ __global__ __launch_bounds__(kEmdThreads) void emd_right_kernel(const float* __r
   }
 }
 
-template <bool FUSED>
+template <bool FUSED, bool GRID>
 __global__ __launch_bounds__(kEmdThreads) void emd_match_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2,
                                                                 float* __restrict__ match, float* __restrict__ temp,
-                                                                float* __restrict__ out, int n, int m, float lvl2) {
+                                                                float* __restrict__ out, int n, int m, float lvl2, int nb,
+                                                                int row0) {
   __shared__ float4 buf[kEmdTile];
   __shared__ float part[kEmdThreads / 64];
-  const EmdPair P = emd_pair(xyz1, xyz2, match, temp, blockIdx.y, n, m);
+  const EmdPair P = emd_pair<GRID>(xyz1, xyz2, match, temp, blockIdx.y, n, m, nb, row0);
   const int k = blockIdx.x * kEmdThreads + threadIdx.x;
   const bool v = k < n;
   const float x1 = v ? P.A[k * 3] : 0.f, y1 = v ? P.A[k * 3 + 1] : 0.f, z1 = v ? P.A[k * 3 + 2] : 0.f;
@@ -309,6 +436,19 @@ extern "C" int gwtf_nn_distance(const float* xyz1, const float* xyz2, float* dis
   return (int)hipGetLastError();
 }
 
+extern "C" int gwtf_chamfer_directed(const float* q, const float* t, float* sum, int* cnt, const float* thr, int n_thr, int nq,
+                                     int nt, int n, int m, void* stream) {
+  if (!q || !t || !sum || nq <= 0 || nt <= 0 || n <= 0 || m <= 0 || n_thr < 0 || n_thr > kCdMaxThr) return GWTF_E_BADARG;
+  if (n_thr > 0 && (!cnt || !thr)) return GWTF_E_BADARG;
+  const long long groups = (nt + kCdGroup - 1) / kCdGroup;
+  if (groups * nq > 0x7fffffffLL) return GWTF_E_BADARG;
+  CdThr th;
+  for (int h = 0; h < kCdMaxThr; ++h) th.v[h] = h < n_thr ? thr[h] : 0.f;
+  hipLaunchKernelGGL(chamfer_directed_kernel, dim3((unsigned)(groups * nq)), dim3(256), 0, (hipStream_t)stream, q, t, sum, cnt, th,
+                     n_thr, nq, nt, n, m);
+  return (int)hipGetLastError();
+}
+
 extern "C" int gwtf_nn_distance_grad(const float* xyz1, const float* xyz2, const float* grad_dist1, const int* idx1,
                                      const float* grad_dist2, const int* idx2, float* grad_xyz1, float* grad_xyz2, int b,
                                      int n, int m, void* stream) {
@@ -323,8 +463,10 @@ extern "C" int gwtf_nn_distance_grad(const float* xyz1, const float* xyz2, const
   return (int)hipGetLastError();
 }
 
+// b pairs; GRID: they are the rows x nb grid starting at A-cloud row0 (b = rows * nb), see emd_pair.
+template <bool GRID>
 static int emd_schedule(const float* xyz1, const float* xyz2, float* match, float* temp, float* out, int b, int n, int m,
-                        hipStream_t st) {
+                        hipStream_t st, int nb = 0, int row0 = 0) {
   hipError_t e = match ? hipMemsetAsync(match, 0, sizeof(float) * (size_t)b * n * m, st)
                        : hipMemsetAsync(out, 0, sizeof(float) * (size_t)b, st);
   if (e != hipSuccess) return (int)e;
@@ -332,12 +474,14 @@ static int emd_schedule(const float* xyz1, const float* xyz2, float* match, floa
   const dim3 gl((n + kEmdThreads - 1) / kEmdThreads, b), gr((m + kEmdThreads - 1) / kEmdThreads, b);
   for (int j = 7; j > -2; --j) {   // approxmatch.cu:31-32
     const float lvl2 = -powf(4.0f, (float)j) * 1.4426950408889634f;
-    hipLaunchKernelGGL(emd_left_kernel, gl, dim3(kEmdThreads), 0, st, xyz1, xyz2, temp, n, m, lvl2);
-    hipLaunchKernelGGL(emd_right_kernel, gr, dim3(kEmdThreads), 0, st, xyz1, xyz2, temp, n, m, lvl2);
+    hipLaunchKernelGGL(emd_left_kernel<GRID>, gl, dim3(kEmdThreads), 0, st, xyz1, xyz2, temp, n, m, lvl2, nb, row0);
+    hipLaunchKernelGGL(emd_right_kernel<GRID>, gr, dim3(kEmdThreads), 0, st, xyz1, xyz2, temp, n, m, lvl2, nb, row0);
     if (match)
-      hipLaunchKernelGGL(emd_match_kernel<false>, gl, dim3(kEmdThreads), 0, st, xyz1, xyz2, match, temp, out, n, m, lvl2);
+      hipLaunchKernelGGL((emd_match_kernel<false, GRID>), gl, dim3(kEmdThreads), 0, st, xyz1, xyz2, match, temp, out, n, m, lvl2,
+                         nb, row0);
     else
-      hipLaunchKernelGGL(emd_match_kernel<true>, gl, dim3(kEmdThreads), 0, st, xyz1, xyz2, match, temp, out, n, m, lvl2);
+      hipLaunchKernelGGL((emd_match_kernel<true, GRID>), gl, dim3(kEmdThreads), 0, st, xyz1, xyz2, match, temp, out, n, m, lvl2,
+                         nb, row0);
   }
   return (int)hipGetLastError();
 }
@@ -345,13 +489,21 @@ static int emd_schedule(const float* xyz1, const float* xyz2, float* match, floa
 extern "C" int gwtf_approx_match(const float* xyz1, const float* xyz2, float* match, float* temp, int b, int n, int m,
                                  void* stream) {
   if (!xyz1 || !xyz2 || !match || !temp || b <= 0 || n <= 0 || m <= 0) return GWTF_E_BADARG;
-  return emd_schedule(xyz1, xyz2, match, temp, nullptr, b, n, m, (hipStream_t)stream);
+  return emd_schedule<false>(xyz1, xyz2, match, temp, nullptr, b, n, m, (hipStream_t)stream);
 }
 
 extern "C" int gwtf_emd_cost(const float* xyz1, const float* xyz2, float* temp, float* out, int b, int n, int m,
                              void* stream) {
   if (!xyz1 || !xyz2 || !temp || !out || b <= 0 || n <= 0 || m <= 0) return GWTF_E_BADARG;
-  return emd_schedule(xyz1, xyz2, nullptr, temp, out, b, n, m, (hipStream_t)stream);
+  return emd_schedule<false>(xyz1, xyz2, nullptr, temp, out, b, n, m, (hipStream_t)stream);
+}
+
+extern "C" int gwtf_emd_cost_pairs(const float* a, const float* b, float* temp, float* out, int na, int nb, int n, int m,
+                                   int row0, int rows, void* stream) {
+  if (!a || !b || !temp || !out || na <= 0 || nb <= 0 || n <= 0 || m <= 0 || row0 < 0 || rows <= 0 || rows > na - row0)
+    return GWTF_E_BADARG;
+  if ((long long)rows * nb > 65535) return GWTF_E_BADARG;   // the pair index is grid.y
+  return emd_schedule<true>(a, b, nullptr, temp, out, rows * nb, n, m, (hipStream_t)stream, nb, row0);
 }
 
 extern "C" int gwtf_match_cost(const float* xyz1, const float* xyz2, const float* match, float* out, int b, int n, int m,

@@ -5,11 +5,18 @@ EMD_CD_F1 :47-107, _pairwise_EMD_CD_F1_SCORE :110-181, knn :185-218, lgan_mmd_co
 and lib/networks/utils.py (get_voxel_occ_dist :45-79, JSD :82-86).  Same names, arguments, return keys and conventions
 (which output is "left" and which "right", 1-based vs 0-based, biased means), so evaluate_ae.py runs unchanged on ROCm.
 The O(N^2) work per cloud pair runs in csrc/gwtf_metrics.hip; everything here is orchestration.
+
+pairwise_matrices / generation_metrics are the device-resident form of the generation evaluation (evaluating.py:191-250): the
+all-pairs matrices come from metrics.chamfer_directed / metrics.emd_cost_pairs (no per-row host loop, a set against itself costs
+one directed pass, every F1 threshold comes out of the same pass), and the result dictionaries are those of compute_all_metrics.
+pairwise_CD / COV / MMD / KNN mirror lib/networks/utils.py:90-144.
 """
 import numpy as np
 import torch
 from scipy.stats import entropy
 
+from . import metrics as _metrics
+from ._lib import GwtfError
 from .metrics import distChamferCUDA, emd_approx, f_score  # noqa: F401  (re-exported: evaluating.py imports them from here)
 
 
@@ -143,6 +150,120 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, f
             one_nn = knn(M_ss, M_rs, M_rr, 1, sqrt=False)
             results.update({'1-NN-%s-%s' % (name, k): v for k, v in one_nn.items() if 'acc' in k})
     return results
+
+
+_NAMES = ('CD', 'EMD', 'F1', 'CD-left', 'CD-right')
+
+
+def _same_clouds(a, b):
+    return a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride()
+
+
+def pairwise_matrices(sample_pcs, ref_pcs, f1_thresholds=(), cd_option=False, one_part_of_cd=False, emd_option=False):
+    """The matrices of _pairwise_EMD_CD_F1_SCORE, computed on the device without its host loop: a dict with 'cd', 'left', 'right',
+    'emd' ((N_sample, N_ref) each; [] when the option is off) and 'f1' = {threshold: matrix} for every threshold asked for.
+    left[i][j] is the mean over the points of sample i of the squared distance to reference j, right[i][j] the mean over the
+    points of reference j; the F1 matrices come from integer counts of the same minima, in _f1's expression.  The same tensor
+    passed twice costs one directed pass (right = left.T: the two directions of a pair are the same numbers)."""
+    f1_thresholds = tuple(f1_thresholds)
+    n, m = sample_pcs.shape[1], ref_pcs.shape[1]
+    out = {'cd': [], 'left': [], 'right': [], 'emd': [], 'f1': {}}
+    if emd_option and n != m:
+        raise GwtfError(f'EMD needs clouds of equal size (emd_approx): got {n} and {m} points')
+    if cd_option or one_part_of_cd or f1_thresholds:
+        sum_sr, cnt_sr = _metrics.chamfer_directed(sample_pcs, ref_pcs, f1_thresholds)
+        if _same_clouds(sample_pcs, ref_pcs):
+            sum_rs, cnt_rs = sum_sr, cnt_sr
+        else:
+            sum_rs, cnt_rs = _metrics.chamfer_directed(ref_pcs, sample_pcs, f1_thresholds)
+        left = sum_sr / float(n)
+        right = (left if sum_rs is sum_sr else sum_rs / float(m)).t().contiguous()
+        if one_part_of_cd:
+            out['left'], out['right'] = left, right
+        if cd_option:
+            out['cd'] = left + right
+        for h, thr in enumerate(f1_thresholds):
+            recall = 100. * (cnt_sr[h].float() / float(n))                       # sample points close to the reference (dl)
+            precision = 100. * (cnt_rs[h].t().float() / float(m))                # reference points close to the sample (dr)
+            out['f1'][thr] = 2. * precision * recall / (precision + recall + 1e-7)
+    else:
+        _metrics._cloud_sets(sample_pcs, ref_pcs, 'sample_pcs', 'ref_pcs')
+    if emd_option:
+        out['emd'] = _metrics.emd_cost_pairs(sample_pcs, ref_pcs) / float(n)
+    return out
+
+
+def generation_metrics(sample_pcs, ref_pcs, f1_threshold_lst=(0.001,), cd_option=False, one_part_of_cd=False, emd_option=False,
+                       f1_option=False):
+    """{threshold: compute_all_metrics(..., f1_threshold=threshold)} for every threshold of the list, from ONE set of
+    sample x ref / ref x ref / sample x sample matrices: distances and EMD are computed once however many thresholds are
+    asked for (evaluating.py:212-216 recomputes them per threshold)."""
+    thresholds = tuple(f1_threshold_lst)
+    opts = dict(f1_thresholds=thresholds if f1_option else (), cd_option=cd_option, one_part_of_cd=one_part_of_cd,
+                emd_option=emd_option)
+    rs = pairwise_matrices(sample_pcs, ref_pcs, **opts)
+    rr = pairwise_matrices(ref_pcs, ref_pcs, **opts)
+    ss = pairwise_matrices(sample_pcs, sample_pcs, **opts)
+    enabled = (cd_option, emd_option, f1_option, one_part_of_cd, one_part_of_cd)
+    shared = {}       # everything that does not depend on the threshold, in compute_all_metrics' key order
+    per_thr = {}
+    for thr in thresholds:
+        def mats(M):
+            return (M['cd'], M['emd'], M['f1'].get(thr, []), M['left'], M['right'])
+        results = {}
+        for name, on, M in zip(_NAMES, enabled, mats(rs)):
+            if on:
+                key = ('mmd', name)
+                if name == 'F1':
+                    res = lgan_mmd_cov(M, 'max')
+                else:
+                    res = shared[key] = shared.get(key) or lgan_mmd_cov(M, 'min')
+                results.update({'%s-%s' % (k, name): v for k, v in res.items()})
+        for name, on, M_rs, M_rr, M_ss in zip(_NAMES, enabled, mats(rs), mats(rr), mats(ss)):
+            if on:
+                key = ('knn', name)
+                if name == 'F1':
+                    one_nn = knn(M_ss, M_rs, M_rr, 1, sqrt=False)
+                else:
+                    one_nn = shared[key] = shared.get(key) or knn(M_ss, M_rs, M_rr, 1, sqrt=False)
+                results.update({'1-NN-%s-%s' % (name, k): v for k, v in one_nn.items() if 'acc' in k})
+        per_thr[thr] = results
+    return per_thr
+
+
+def pairwise_CD(clouds1, clouds2, bs=2048):
+    """Chamfer distance (sum of the two directed means) of every cloud of ``clouds1`` against every cloud of ``clouds2``
+    (reference utils.py:90-117) -> (N1, N2) float32 on the device.  ``bs`` (the reference's chunk size) is accepted and ignored:
+    nothing is chunked."""
+    return pairwise_matrices(clouds1, clouds2, cd_option=True)['cd']
+
+
+def COV(dists, axis=1):
+    """Coverage (reference utils.py:120-121): the share of the clouds along ``axis`` that are the nearest one (argmin along ``axis``)
+    of at least one cloud of the other axis."""
+    return float(dists.min(axis)[1].unique().numel()) / float(dists.shape[axis])
+
+
+def MMD(dists, axis=1):
+    """Minimum matching distance (reference utils.py:124-125): for every cloud along ``axis`` the distance to its nearest cloud
+    of the other axis, averaged."""
+    return float(dists.min(1 - axis)[0].float().mean())
+
+
+def KNN(Mxx, Mxy, Myy, k, sqrt=False):
+    """Leave-one-out k-NN accuracy on the joint distance matrix (reference utils.py:128-144) as a float.  Unlike knn above the
+    labels are -1 (first set) / +1 (second set) and a cloud is predicted +1 when the sum of its neighbours' labels is >= 0 --
+    at even k a tie goes to the SECOND set, where knn's count >= k/2 of 1/0 labels sends it to the first."""
+    n0, n1 = Mxx.size(0), Myy.size(0)
+    label = torch.cat((-torch.ones(n0), torch.ones(n1))).to(Mxx)
+    M = torch.cat((torch.cat((Mxx, Mxy), 1), torch.cat((Mxy.transpose(0, 1), Myy), 1)), 0)
+    if sqrt:
+        M = M.abs().sqrt()
+    M = M + torch.diag(torch.full((n0 + n1,), float('inf')).to(Mxx))
+    idx = M.topk(k, 0, False)[1]                                   # the k nearest other clouds of every column
+    votes = label[idx].sum(0)
+    pred = torch.where(votes >= 0, torch.ones_like(votes), -torch.ones_like(votes))
+    return float((pred == label).float().mean())
 
 
 def get_voxel_occ_dist(all_clouds, clouds_flag='gen', res=28, bound=0.5, bs=128, warning=True):

@@ -6,6 +6,9 @@ and return values; the compute runs in csrc/gwtf_metrics.hip through the C ABI (
 contiguous and on a HIP device -- the checks the reference's extension applies (structural_loss.cpp:10-12); there is no
 CPU path.
 """
+import ctypes
+
+import numpy as np
 import torch
 from torch.autograd import Function
 
@@ -109,6 +112,63 @@ class MatchCostFunction(Function):
 
 
 match_cost = MatchCostFunction.apply
+
+
+def _cloud_sets(a, b, na, nb):
+    """The checks of _sets for two sets of clouds that need not agree in cloud count: (na, n), (nb, m)."""
+    if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3:
+        raise GwtfError(f'cloud sets must be (nq,n,3) and (nt,m,3): got {tuple(a.shape)} and {tuple(b.shape)}')
+    _ptr(a, na), _ptr(b, nb)
+    if min(a.shape[0], a.shape[1], b.shape[0], b.shape[1]) == 0:
+        raise GwtfError('empty point set')
+
+
+MAX_THRESHOLDS = 8      # per gwtf_chamfer_directed call (the thresholds travel as a kernel argument)
+
+
+def chamfer_directed(q, t, thresholds=()):
+    """Every cloud of ``q`` (nq,n,3) against every cloud of ``t`` (nt,m,3), one direction, reduced on the device:
+    sum (nq,nt) float32 = sum over the points of q_i of the squared distance to the nearest point of t_j (the minimum is
+    nn_distance's dist1, bit for bit), cnt (T,nq,nt) int32 = how many of those minima are < thresholds[h], compared in
+    float32.  No (pairs, n) intermediate and no expanded copy of either set; repeated calls give identical bits."""
+    _cloud_sets(q, t, 'q', 't')
+    nq, n, nt, m = q.shape[0], q.shape[1], t.shape[0], t.shape[1]
+    thr = np.asarray(list(thresholds), dtype=np.float32).reshape(-1)
+    dev = q.device
+    out = torch.empty(nq, nt, device=dev, dtype=torch.float32)
+    cnt = torch.empty(len(thr), nq, nt, device=dev, dtype=torch.int32)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        for h0 in range(0, max(len(thr), 1), MAX_THRESHOLDS):      # more than 8 thresholds: further passes
+            part = np.ascontiguousarray(thr[h0:h0 + MAX_THRESHOLDS])
+            check(L.gwtf_chamfer_directed(_ptr(q, 'q'), _ptr(t, 't'), out.data_ptr(), cnt[h0:].data_ptr() if len(part) else None,
+                                          part.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if len(part) else None, len(part),
+                                          nq, nt, n, m, _stream(q)))
+    return out, cnt
+
+
+MAX_PAIRS_PER_LAUNCH = 65535      # gwtf_emd_cost_pairs: the pair index is a grid's second dimension
+
+
+def emd_cost_pairs(a, b, max_temp_bytes=256 << 20):
+    """Fused approximate-matching cost (what match_cost returns when no gradient is wanted) of every cloud of ``a`` (na,n,3)
+    against every cloud of ``b`` (nb,m,3): (na,nb) float32, not normalised.  No expanded copies; the rows of the result are
+    walked in blocks whose (pairs, 2(n+m)) scratch stays within ``max_temp_bytes`` (at least one row per block)."""
+    _cloud_sets(a, b, 'a', 'b')
+    na, n, nb, m = a.shape[0], a.shape[1], b.shape[0], b.shape[1]
+    if nb > MAX_PAIRS_PER_LAUNCH:
+        raise GwtfError(f'emd_cost_pairs: at most {MAX_PAIRS_PER_LAUNCH} clouds in b (got {nb}); split b')
+    per_row = nb * 2 * (n + m)                                    # floats of scratch per row of the result
+    rows = max(1, min(na, int(max_temp_bytes) // (4 * per_row), MAX_PAIRS_PER_LAUNCH // nb))
+    out = torch.empty(na, nb, device=a.device, dtype=torch.float32)
+    temp = torch.empty(rows * per_row, device=a.device, dtype=torch.float32)
+    L = _lib.lib()
+    with torch.cuda.device(a.device):
+        for row0 in range(0, na, rows):
+            r = min(rows, na - row0)
+            check(L.gwtf_emd_cost_pairs(_ptr(a, 'a'), _ptr(b, 'b'), _ptr(temp, 'temp'), out[row0:].data_ptr(), na, nb, n, m,
+                                        row0, r, _stream(a)))
+    return out
 
 
 def distChamferCUDA(x, y):

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define GWTF_ABI_VERSION 9
+#define GWTF_ABI_VERSION 10
 #define GWTF_E_BADARG 10001   /* shape / mode / width outside what the kernels support */
 #define GWTF_E_UNSUPPORTED 10002   /* a layer-width list no kernel instantiation was built for */
 #define GWTF_MODE_DIRECT 0    /* sampling direction  base -> data (reference models.py:202) */
@@ -327,6 +327,19 @@ int gwtf_approx_match(const float* xyz1, const float* xyz2, float* match, float*
  * accumulates sum w * distance level by level.  What match_cost.py:10-23 computes when no gradient is wanted
  * (evaluation_metrics.py:25-30 is its only caller); temp as for gwtf_approx_match. */
 int gwtf_emd_cost(const float* xyz1, const float* xyz2, float* temp, float* out, int b, int n, int m, void* stream);
+/* The fused cost over a GRID of pairs, without expanded copies: a [na][n][3], b [nb][m][3]; out[r][c] (rows x nb, zeroed by the
+ * call) is what gwtf_emd_cost gives for the pair (a[row0 + r], b[c]) -- same nine levels, same sweeps.  temp holds at least
+ * rows * nb * 2(n+m) floats; rows * nb <= 65535 (the caller walks row0 in blocks). */
+int gwtf_emd_cost_pairs(const float* a, const float* b, float* temp, float* out, int na, int nb, int n, int m, int row0,
+                        int rows, void* stream);
+/* Directed Chamfer reduction over all ordered pairs of two sets of clouds (the all-pairs matrices of evaluation_metrics.py:110-181
+ * without its host loop): q [nq][n][3], t [nt][m][3];
+ *   sum[i][j]    = sum over the points a of q_i of min_{b in t_j} |a - b|^2      (the minimum is dist1 of gwtf_nn_distance, bit for bit)
+ *   cnt[h][i][j] = number of points of q_i whose minimum is < thr[h], compared in float32
+ * thr: HOST array of n_thr <= 8 values, read during the call; with n_thr == 0 cnt and thr may be NULL.  Reductions are in a fixed
+ * order inside one workgroup per pair: repeated calls give identical bits. */
+int gwtf_chamfer_directed(const float* q, const float* t, float* sum, int* cnt, const float* thr, int n_thr, int nq, int nt,
+                          int n, int m, void* stream);
 /* Replaces MatchCost (structural_loss.cpp:39-55, approxmatch.cu:184-224): out [b] = sum match * distance. */
 int gwtf_match_cost(const float* xyz1, const float* xyz2, const float* match, float* out, int b, int n, int m,
                     void* stream);
