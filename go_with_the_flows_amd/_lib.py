@@ -112,6 +112,8 @@ _SIGNATURES = {
     'gwtf_resnet_packed_floats': (ctypes.c_size_t, [ctypes.c_int]),
     'gwtf_resnet_work_floats': (ctypes.c_size_t, [ctypes.c_int] * 4),
     'gwtf_resnet_forward': (ctypes.c_int, [_c_fp] * 4 + [ctypes.c_int] * 5 + [_c_fp]),
+    'gwtf_cloud_partials': (ctypes.c_int, [ctypes.c_int]),
+    'gwtf_sample_clouds': (ctypes.c_int, [ctypes.c_void_p]),
 }
 
 PHASE_FWD_INIT, PHASE_FWD_A, PHASE_FWD_B, PHASE_BWD_A, PHASE_BWD_B, PHASE_BWD_C = range(6)
@@ -134,6 +136,17 @@ class StackArgs(ctypes.Structure):
                  ('p_stride_k', ctypes.c_size_t), ('out_stride_k', ctypes.c_size_t)] +
                 [(n, ctypes.c_int) for n in ('K', 'B', 'N', 'C', 'f', 'pattern0', 'mode', 'tune')] +
                 [('eps', ctypes.c_float), ('stream', ctypes.c_void_p)])
+
+
+class CloudArgs(ctypes.Structure):
+    """GwtfCloudArgs of include/gwtf.h (one batch of sampled clouds): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in (
+                    'rows', 'vertices', 'faces', 'thresholds', 'vertices_bounds', 'faces_bounds', 'search_len', 'orig_c', 'orig_s',
+                    'cloud', 'eval_cloud', 'partials', 'state', 'words', 's1', 's2', 'normals')] +
+                [(n, ctypes.c_int) for n in ('B', 'M', 'n_shapes', 'rescale', 'recenter', 'translate', 'scale', 'noise', 'center',
+                                             'tune')] +
+                [('shift', ctypes.c_float * 3), ('scale_div', ctypes.c_float), ('noise_scale', ctypes.c_float),
+                 ('stream', ctypes.c_void_p)])
 
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1,0 +1,298 @@
+"""Training batches drawn on the device (csrc/gwtf_clouds.hip): the reference's ShapeNetCoreDataset.__getitem__
+(lib/datasets/datasets.py:69-106) -- sample_cloud (lib/datasets/cloud_sampling.py:4-32) and the composed cloud transformations
+(lib/datasets/cloud_transformations.py:79-103) -- for a whole batch in one call, from meshes that stay in device memory.
+
+    store = MeshStore.from_h5('.../meshes.h5', 'train', device='cuda')
+    loader = DeviceCloudLoader(store, 64, 2048, transform=CloudTransform.from_config(**config))
+    for batch in loader:                       # {'cloud': (B,3,N), 'eval_cloud': (B,3,N), 'orig_c': (B,3), 'orig_s': (B,)} on the device
+
+Host work happens once, at construction: the per-face integer thresholds of every shape's area CDF, built with the reference's own
+arithmetic.  There is no CPU sampling path: sample_clouds on a CPU store raises.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import GwtfError
+
+TWO32 = 4294967296.0
+
+
+def face_cdf(vertices_c, faces_vc):
+    """(probs float32, cdf float64) of one mesh exactly as sample_cloud + RandomState.choice compute them
+    (cloud_sampling.py:5-10; choice: cdf = cumsum(float64(p)), cdf /= cdf[-1])."""
+    polygons = np.asarray(vertices_c, np.float32)[np.asarray(faces_vc).astype(np.int64)]
+    cross = np.cross(polygons[:, 2] - polygons[:, 0], polygons[:, 2] - polygons[:, 1])
+    areas = np.sqrt((cross**2).sum(1)) / 2.0
+    probs = areas / areas.sum()
+    cdf = np.cumsum(probs.astype(np.float64))
+    cdf /= cdf[-1]
+    return probs, cdf
+
+
+def face_thresholds(cdf):
+    """(T uint32, search_len): T[k] = ceil(cdf[k] * 2^32) -- exact in float64, a scaling by a power of two -- so that for a 32-bit
+    word w   #{k : T[k] <= w} == np.searchsorted(cdf, w * 2^-32, 'right').   Thresholds that reach 2^32 (the last face's always
+    does) lie above every word: they are stored as 0xffffffff and left out of the search, whose length is the second result."""
+    t = np.ceil(cdf * TWO32)
+    search_len = int(np.count_nonzero(t < TWO32))
+    if np.any(np.diff(t) < 0):
+        raise GwtfError('face CDF is not monotone')
+    return np.minimum(t, TWO32 - 1).astype(np.uint32), search_len
+
+
+def search_faces(thresholds, search_len, words):
+    """The device's face search on the host (numpy): #{k < search_len : T[k] <= w}."""
+    return np.searchsorted(thresholds[:search_len], np.asarray(words, np.uint32), side='right')
+
+
+def _take_slices(data, bounds, keep):
+    """The slices data[bounds[i]:bounds[i+1]] for i in keep, repacked -> (data, bounds)."""
+    bounds = np.asarray(bounds).astype(np.int64)
+    parts = [data[bounds[i]:bounds[i + 1]] for i in keep]
+    return (np.concatenate(parts) if parts else data[:0]), np.cumsum([0] + [len(p) for p in parts]).astype(np.int64)
+
+
+class MeshStore:
+    """The packed meshes of one part of meshes.h5 (preprocess_ShapeNetCore.py:55-69) on one device, with their face thresholds."""
+
+    def __init__(self):
+        raise TypeError('use MeshStore.from_arrays / MeshStore.from_h5')
+
+    @classmethod
+    def from_arrays(cls, vertices_c, faces_vc, vertices_c_bounds, faces_bounds, orig_c=None, orig_s=None, device='cuda'):
+        self = object.__new__(cls)
+        vertices = np.ascontiguousarray(vertices_c, dtype=np.float32)
+        faces = np.ascontiguousarray(faces_vc).astype(np.int64)
+        vb = np.asarray(vertices_c_bounds).astype(np.int64)
+        fb = np.asarray(faces_bounds).astype(np.int64)
+        if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+            raise GwtfError('vertices_c must be (V,3) and faces_vc (F,3)')
+        n = len(vb) - 1
+        if n < 1 or len(fb) != n + 1:
+            raise GwtfError('vertices_c_bounds and faces_bounds must both hold n_shapes + 1 entries')
+        if vb[0] < 0 or fb[0] < 0 or vb[-1] > len(vertices) or fb[-1] > len(faces) or np.any(np.diff(vb) < 0) or np.any(np.diff(fb) < 0):
+            raise GwtfError('bounds are not ascending offsets into vertices_c / faces_vc')
+        thresholds = np.full(len(faces), 0xffffffff, np.uint32)
+        search_len = np.zeros(n, np.int32)
+        for i in range(n):
+            f = faces[fb[i]:fb[i + 1]]
+            v = vertices[vb[i]:vb[i + 1]]
+            if len(f) == 0:
+                raise GwtfError(f'shape {i} has no faces')
+            if len(f) >= 2**31:
+                raise GwtfError(f'shape {i} has too many faces')
+            if f.min() < 0 or f.max() >= len(v):
+                raise GwtfError(f'shape {i}: a face names a vertex outside the shape\'s {len(v)} vertices')
+            with np.errstate(invalid='ignore', divide='ignore'):
+                _, cdf = face_cdf(v, f)
+            if not np.all(np.isfinite(cdf)) or not cdf[-1] == 1.0:
+                raise GwtfError(f'shape {i} has zero total face area')
+            thresholds[fb[i]:fb[i + 1]], search_len[i] = face_thresholds(cdf)
+        self.n_shapes = n
+        self.thresholds_host, self.search_len_host = thresholds, search_len
+        self.vertices_bounds_host, self.faces_bounds_host = vb, fb
+        self.device = torch.device(device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        self.vertices = up(vertices)
+        self.faces = up(faces.astype(np.int32))
+        self.thresholds = up(thresholds.view(np.int32))          # the bits of the uint32 thresholds
+        self.vertices_bounds, self.faces_bounds, self.search_len = up(vb), up(fb), up(search_len)
+        self.orig_c = None if orig_c is None else up(np.asarray(orig_c, np.float32).reshape(n, 3))
+        self.orig_s = None if orig_s is None else up(np.asarray(orig_s, np.float32).reshape(n))
+        self._work = {}
+        self._state = None
+        return self
+
+    @classmethod
+    def from_h5(cls, path, part='train', return_original_scale=True, chosen_label=None, device='cuda'):
+        """The dataset reads of ShapeNetCoreDataset.choose_part / __getitem__ (datasets.py:33-57,78-85), once for the whole part;
+        chosen_label keeps the shapes of one class, as the dataset's chosen_label_inds does."""
+        try:
+            import h5py
+        except ImportError as e:
+            raise GwtfError('MeshStore.from_h5 needs h5py, which is not installed; read the datasets yourself and use '
+                            'MeshStore.from_arrays') from e
+        with h5py.File(path, 'r') as fin:
+            v, f, vb, fb = [np.array(fin[part + '_' + k]) for k in ('vertices_c', 'faces_vc', 'vertices_c_bounds', 'faces_bounds')]
+            orig_c, orig_s = [np.array(fin[part + '_' + k]) for k in ('orig_c', 'orig_s')] if return_original_scale else [None, None]
+            keep = None if chosen_label is None else (np.array(fin[part + '_labels'], dtype=np.uint8) == chosen_label).nonzero()[0]
+        if keep is not None:
+            v, vb = _take_slices(v, vb, keep)
+            f, fb = _take_slices(f, fb, keep)
+            orig_c, orig_s = (None, None) if orig_c is None else (orig_c[keep], orig_s[keep])
+        return cls.from_arrays(v, f, vb, fb, orig_c=orig_c, orig_s=orig_s, device=device)
+
+    def __len__(self):
+        return self.n_shapes
+
+
+class CloudTransform:
+    """The record of cloud transformations the kernel fuses, in ComposeCloudTransformation's order
+    (cloud_transformations.py:79-96): Scale2OrigCloud, TranslateCloud, ScaleCloud, AddNoise2Cloud, CenterCloud."""
+
+    def __init__(self, rescale2orig=False, recenter2orig=False, translate=False, translate_shift=(0.0, 0.0, 0.0), scale=False,
+                 scale_scale=1.0, noise=False, noise_scale=1.0, center=False):
+        self.rescale2orig, self.recenter2orig = bool(rescale2orig), bool(recenter2orig)
+        self.translate, self.scale, self.noise, self.center = bool(translate), bool(scale), bool(noise), bool(center)
+        self.translate_shift = tuple(float(np.float32(v)) for v in np.asarray(translate_shift, np.float32).reshape(-1)) \
+            if self.translate else (0.0, 0.0, 0.0)
+        if len(self.translate_shift) != 3:
+            raise ValueError('cloud_translate_shift must hold three values')
+        self.scale_scale = float(np.float32(scale_scale)) if self.scale else 1.0
+        self.noise_scale = float(np.float32(noise_scale)) if self.noise else 1.0
+        if self.scale and not self.scale_scale > 0:
+            raise ValueError('cloud_scale_scale must be positive')
+        if self.noise and not self.noise_scale > 0:
+            raise ValueError('cloud_noise_scale must be positive')
+
+    @classmethod
+    def from_config(cls, **kwargs):
+        """From the reference's config keys; keys it does not know (the rest of a config file) are ignored."""
+        if kwargs.get('cloud_random_rotate'):
+            raise NotImplementedError(
+                'cloud_random_rotate: the reference\'s Random3DRotation raises NameError (Rotation is never imported, '
+                'cloud_transformations.py:70) and would compute eval_cloud from the already rotated cloud; it is not reproduced')
+        return cls(rescale2orig=kwargs.get('cloud_rescale2orig', False), recenter2orig=kwargs.get('cloud_recenter2orig', False),
+                   translate=kwargs.get('cloud_translate', False), translate_shift=kwargs.get('cloud_translate_shift') or (0, 0, 0),
+                   scale=kwargs.get('cloud_scale', False), scale_scale=kwargs.get('cloud_scale_scale') or 1.0,
+                   noise=kwargs.get('cloud_noise', False), noise_scale=kwargs.get('cloud_noise_scale') or 1.0,
+                   center=kwargs.get('cloud_center', False))
+
+
+def make_state(seed, device='cuda', call=0):
+    """The device-resident (seed, call) pair of the sampler: every call (and every replay of a captured call) reads it and leaves
+    call one higher."""
+    seed, call = int(seed) & (2**64 - 1), int(call)
+    if not 0 <= call < 2**60:
+        raise ValueError('call must lie in [0, 2^60)')
+    return torch.tensor([seed - 2**64 if seed >= 2**63 else seed, call], dtype=torch.int64, device=device)
+
+
+def cloud_partials(M):
+    return _lib.lib().gwtf_cloud_partials(int(M))
+
+
+def sample_clouds(store, rows, cloud_size, return_eval_cloud=True, transform=None, state=None, explicit=None, out=None):
+    """One batch: rows (B,) int32 shape indices on the store's device -> {'cloud': (B,3,cloud_size)[, 'eval_cloud'][, 'orig_c',
+    'orig_s']}, the keys and shapes of a collated reference batch.  Enqueued on the current stream; nothing waits for the device.
+
+    state: make_state(seed) (default: one the store keeps, seed 0).  explicit: {'words': (B,M) int32 bits of the uint32 face words,
+    's1', 's2': (B,M) float32, 'normals': (B,3,M) float32 when noise is on} replaces Philox (M = 2 * cloud_size with an eval cloud).
+    The scratch of a given (B, M) is allocated on the first call and kept on the store.  The returned tensors are fresh ones from
+    torch's allocator (which a graph capture records like any other); pass out={'cloud': ..., 'eval_cloud': ...} to write into
+    tensors of your own and allocate nothing at all."""
+    if store.device.type != 'cuda':
+        raise GwtfError(f'the store lives on {store.device}: sampling runs on a HIP device only, there is no CPU path')
+    if rows.dtype != torch.int32 or rows.dim() != 1 or rows.device != store.device or not rows.is_contiguous():
+        raise GwtfError('rows must be a contiguous 1-d int32 tensor on the store\'s device')
+    t = transform if transform is not None else _IDENTITY
+    if (t.rescale2orig and store.orig_s is None) or (t.recenter2orig and store.orig_c is None):
+        raise GwtfError('the transformation scales back to the original frame but the store has no orig_c / orig_s')
+    B, N = rows.numel(), int(cloud_size)
+    M = 2 * N if return_eval_cloud else N
+    dev = store.device
+    if out is None:
+        out = {'cloud': torch.empty(B, 3, N, device=dev, dtype=torch.float32)}
+        if return_eval_cloud:
+            out['eval_cloud'] = torch.empty(B, 3, N, device=dev, dtype=torch.float32)
+    res = {'cloud': out['cloud']}
+    if return_eval_cloud:
+        res['eval_cloud'] = out['eval_cloud']
+    for k, v in res.items():
+        if tuple(v.shape) != (B, 3, N):
+            raise GwtfError(f'out[{k!r}] is {tuple(v.shape)}, expected {(B, 3, N)}')
+    partials = None
+    if t.center:
+        partials = store._work.get((B, M))
+        if partials is None:
+            partials = store._work[(B, M)] = torch.empty(B, max(1, cloud_partials(M)), 6, device=dev, dtype=torch.float32)
+    if state is None:
+        if store._state is None:
+            store._state = make_state(0, dev)
+        state = store._state
+    if state.dtype != torch.int64 or state.numel() != 2 or state.device != dev:
+        raise GwtfError('state must come from make_state(seed, device) on the store\'s device')
+    ex = {}
+    if explicit is not None:
+        for k, shape, dt in (('words', (B, M), torch.int32), ('s1', (B, M), torch.float32), ('s2', (B, M), torch.float32)) + \
+                ((('normals', (B, 3, M), torch.float32),) if t.noise else ()):
+            v = explicit[k]
+            if tuple(v.shape) != shape or v.dtype != dt or v.device != dev or not v.is_contiguous():
+                raise GwtfError(f'explicit[{k!r}] must be a contiguous {dt} tensor of shape {shape} on the store\'s device')
+            ex[k] = v.data_ptr()
+    ptr = lambda x: None if x is None else x.data_ptr()
+    a = _lib.CloudArgs(
+        rows=rows.data_ptr(), vertices=store.vertices.data_ptr(), faces=store.faces.data_ptr(), thresholds=store.thresholds.data_ptr(),
+        vertices_bounds=store.vertices_bounds.data_ptr(), faces_bounds=store.faces_bounds.data_ptr(),
+        search_len=store.search_len.data_ptr(), orig_c=ptr(store.orig_c), orig_s=ptr(store.orig_s),
+        cloud=_lib._ptr(res['cloud'], 'cloud'), eval_cloud=_lib._ptr(res.get('eval_cloud'), 'eval_cloud'), partials=ptr(partials),
+        state=state.data_ptr(), words=ex.get('words'), s1=ex.get('s1'), s2=ex.get('s2'), normals=ex.get('normals'),
+        B=B, M=M, n_shapes=store.n_shapes, rescale=t.rescale2orig, recenter=t.recenter2orig, translate=t.translate, scale=t.scale,
+        noise=t.noise, center=t.center, tune=_lib.tune_word(), shift=(ctypes.c_float * 3)(*t.translate_shift),
+        scale_div=t.scale_scale, noise_scale=t.noise_scale, stream=torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().gwtf_sample_clouds(ctypes.addressof(a)))
+    if store.orig_c is not None or store.orig_s is not None:
+        inside = rows.clamp(0, store.n_shapes - 1)            # a row outside the store has NaN points; its gather must stay in bounds
+        if store.orig_c is not None:
+            res['orig_c'] = store.orig_c.index_select(0, inside)
+        if store.orig_s is not None:
+            res['orig_s'] = store.orig_s.index_select(0, inside)
+    return res
+
+
+_IDENTITY = CloudTransform()
+
+
+class DeviceCloudLoader:
+    """Stands where DataLoader(ShapeNetCoreDataset(...), batch_size, shuffle=True, drop_last=True) stood (train_ae.py:85-116): an
+    iterable of device batches.  The epoch's order is a host permutation from (seed, epoch) -- torch.randperm under a generator
+    seeded seed + epoch, and for world_size > 1 the padding and stride of torch.utils.data.DistributedSampler, whose indices a rank
+    therefore reproduces; the points come from the device sampler, whose state lives on the device and advances by itself."""
+
+    def __init__(self, store, batch_size, cloud_size, transform=None, shuffle=True, drop_last=True, seed=0, rank=0, world_size=1,
+                 return_eval_cloud=True):
+        if not 0 <= rank < world_size:
+            raise ValueError('rank must lie in [0, world_size)')
+        if batch_size < 1:
+            raise ValueError('batch_size must be positive')
+        self.store, self.batch_size, self.cloud_size, self.transform = store, int(batch_size), int(cloud_size), transform
+        self.shuffle, self.drop_last, self.seed, self.rank, self.world_size = bool(shuffle), bool(drop_last), int(seed), rank, world_size
+        self.return_eval_cloud = bool(return_eval_cloud)
+        self.epoch = 0
+        self.num_samples = -(-len(store) // world_size)               # DistributedSampler, drop_last=False: ceil
+        self._state = None
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return self.num_samples // self.batch_size if self.drop_last else -(-self.num_samples // self.batch_size)
+
+    def index_plan(self, epoch=None):
+        """This rank's shape indices for one epoch, in order (host, int64 numpy); batches are consecutive slices of it."""
+        epoch = self.epoch if epoch is None else int(epoch)
+        n = len(self.store)
+        if self.shuffle:
+            g = torch.Generator()
+            g.manual_seed(self.seed + epoch)
+            idx = torch.randperm(n, generator=g).tolist()
+        else:
+            idx = list(range(n))
+        total = self.num_samples * self.world_size
+        pad = total - len(idx)
+        if pad > 0:
+            idx += (idx * -(-pad // len(idx)))[:pad]
+        return np.asarray(idx[self.rank:total:self.world_size], np.int64)
+
+    def __iter__(self):
+        dev = self.store.device
+        if self._state is None:                                       # ranks draw from different Philox keys
+            self._state = make_state(self.seed + 0x9E3779B97F4A7C15 * self.rank, dev)
+        rows = torch.from_numpy(self.index_plan().astype(np.int32)).to(dev)
+        for b in range(len(self)):
+            yield sample_clouds(self.store, rows[b * self.batch_size:(b + 1) * self.batch_size], self.cloud_size,
+                                self.return_eval_cloud, self.transform, self._state)

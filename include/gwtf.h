@@ -536,6 +536,53 @@ size_t gwtf_resnet_work_floats(int B, int H, int W, int tune);
 int gwtf_resnet_forward(const float* image, const float* packed, float* out, float* work, int B, int H, int W, int num_classes,
                         int tune, void* stream);
 
+/* Training batches drawn on the device (csrc/gwtf_clouds.hip): what ShapeNetCoreDataset.__getitem__ (lib/datasets/datasets.py:69-106)
+ * does per item on the host -- sample_cloud (lib/datasets/cloud_sampling.py:4-32) and the composed cloud transformations
+ * (lib/datasets/cloud_transformations.py:6-64,79-103, Random3DRotation excluded) -- for B shapes of a store of packed meshes (the
+ * datasets of meshes.h5, preprocess_ShapeNetCore.py:55-69) in one launch plus a finishing launch.
+ *   Face of a point: #{k < search_len : thresholds[k] <= w} for a 32-bit word w, thresholds[k] = ceil(cdf[k] * 2^32) of the float64
+ *   CDF RandomState.choice builds -- np.searchsorted(cdf, w * 2^-32, 'right') for every w.  search_len counts the shape's thresholds
+ *   below 2^32 (the others can never be reached and are not read; store them as 0xffffffff), so the count stays at or below the last
+ *   face with area, and leading zero-area faces (threshold 0) are always counted past.
+ *   Point: (v0 + s1 (v1 - v0)) + s2 (v2 - v0) in float32, (s1, s2) folded to 1 - s when s1 + s2 > 1.  Point j of row r goes to
+ *   cloud[r][:][j] -- with an eval cloud (M even) to cloud[r][:][j/2] for even j, eval_cloud[r][:][j/2] for odd j.
+ *   Randomness: Philox4x32-10, key (seed lo, seed hi), counter (j, r, call lo, call hi | stream << 28), call < 2^60; stream 0 gives
+ *   w = word 0, s1 = (word 1 >> 8) 2^-24, s2 = (word 2 >> 8) 2^-24; stream 1 Box-Muller normals from (word 0, word 1) -> x, y and
+ *   (word 2, word 3) -> z.  With `words` non-NULL the draws are read instead (tests, fixtures).
+ *   The finishing launch subtracts the per-cloud means (fixed summation order, no float atomics) and stores call + 1 into state[1].
+ * A row index outside [0, n_shapes) yields NaN points and reads nothing. */
+typedef struct GwtfCloudArgs {
+  const int* rows;                   /* [B] shape indices, repeats allowed */
+  const float* vertices;             /* [V][3] all shapes' vertices */
+  const int* faces;                  /* [F][3] vertex indices LOCAL to the shape's vertex slice */
+  const unsigned* thresholds;        /* [F] */
+  const long long* vertices_bounds;  /* [n_shapes + 1] */
+  const long long* faces_bounds;     /* [n_shapes + 1] */
+  const int* search_len;             /* [n_shapes] */
+  const float* orig_c;               /* [n_shapes][3], read when recenter */
+  const float* orig_s;               /* [n_shapes], read when rescale */
+  float* cloud;                      /* [B][3][N], N = M / 2 with an eval cloud, else M */
+  float* eval_cloud;                 /* [B][3][N] or NULL */
+  float* partials;                   /* [B][gwtf_cloud_partials(M)][6] scratch, written and read when center */
+  unsigned long long* state;         /* {seed, call} */
+  const unsigned* words;             /* explicit draws: [B][M] face words, or NULL (Philox) */
+  const float* s1;                   /* [B][M] in [0, 1) */
+  const float* s2;                   /* [B][M] */
+  const float* normals;              /* [B][3][M] standard normals, read when noise */
+  int B, M, n_shapes;
+  int rescale, recenter, translate, scale, noise, center;   /* cloud_transformations.py:79-96, applied in this order */
+  int tune;                          /* low 16 bits: points a workgroup walks (a multiple of 256; 0: 1024); results do not depend on it */
+  float shift[3];                    /* TranslateCloud: x - shift */
+  float scale_div;                   /* ScaleCloud: x / scale_div, > 0 */
+  float noise_scale;                 /* AddNoise2Cloud: x + noise_scale * z, > 0 */
+  void* stream;
+} GwtfCloudArgs;
+/* Tiles of 256 points whose partial sums one row leaves in `partials` (reference cloud_transformations.py:56-64). */
+int gwtf_cloud_partials(int M);
+/* GWTF_E_BADARG without a launch: a NULL record or required pointer, B < 1, M < 1, odd M with an eval cloud, scale_div / noise_scale
+ * <= 0 where enabled, explicit draws given in part (reference cloud_sampling.py:4-32). */
+int gwtf_sample_clouds(const GwtfCloudArgs* args);
+
 #ifdef __cplusplus
 }
 #endif
