@@ -114,6 +114,9 @@ _SIGNATURES = {
     'gwtf_resnet_forward': (ctypes.c_int, [_c_fp] * 4 + [ctypes.c_int] * 5 + [_c_fp]),
     'gwtf_cloud_partials': (ctypes.c_int, [ctypes.c_int]),
     'gwtf_sample_clouds': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_route_tiles': (ctypes.c_int, [ctypes.c_int] * 3),
+    'gwtf_mixture_route': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_stack_forward_routed': (ctypes.c_int, [ctypes.c_void_p]),
 }
 
 PHASE_FWD_INIT, PHASE_FWD_A, PHASE_FWD_B, PHASE_BWD_A, PHASE_BWD_B, PHASE_BWD_C = range(6)
@@ -147,6 +150,20 @@ class CloudArgs(ctypes.Structure):
                                              'tune')] +
                 [('shift', ctypes.c_float * 3), ('scale_div', ctypes.c_float), ('noise_scale', ctypes.c_float),
                  ('stream', ctypes.c_void_p)])
+
+
+class RouteArgs(ctypes.Structure):
+    """GwtfRouteArgs of include/gwtf.h (components, base samples and tile layout of S generated clouds): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('logits', 'mu0', 'lv0', 'state', 'words', 'labels_in', 'normals', 'z0_in', 'thresholds',
+                                                'tile_comp', 'perm', 'zp', 'labels')] +
+                [(n, ctypes.c_int) for n in ('S', 'n', 'K', 'P', 'mu0_stride', 'lv0_stride')] + [('stream', ctypes.c_void_p)])
+
+
+class RoutedStackArgs(ctypes.Structure):
+    """GwtfRoutedStackArgs of include/gwtf.h (the stack launch on the routed layout): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('zp', 'weights', 'film', 'tile_comp', 'perm', 'out', 'logdet')] +
+                [(n, ctypes.c_int) for n in ('K', 'S', 'n', 'P', 'C', 'f', 'pattern0', 'tune')] +
+                [('eps', ctypes.c_float), ('stream', ctypes.c_void_p)])
 
 
 EXPORTS = tuple(_SIGNATURES)
@@ -412,3 +429,80 @@ def stack_plan(K, B, N, f, segments=None, word=None):
     out = (ctypes.c_int * 4)()
     check(lib().gwtf_stack_plan(seg, K, B, N, f, _TUNE[0] if word is None else int(word), out))
     return out[0], out[1]
+
+
+# ---- device-resident generation (csrc/gwtf_route.hip, the ROUTED stack launch) ---------------------------------------------------
+def route_tiles(n, K, P):
+    """Tile slots per shape of the routed layout, floor((n + K (P - 1)) / P) -- host-only; 0 for sizes the launches reject."""
+    return lib().gwtf_route_tiles(int(n), int(K), int(P))
+
+
+def route_points_per_tile(S, n, K, f):
+    """P of a routed generation call: the stack's tile choice for S shapes whose n points split evenly over the K components (the
+    expected split; the forced-tile bits of the tuning word apply) -- host-only."""
+    cuts = [(k * n) // K for k in range(K + 1)]
+    return 4 * stack_plan(K, S, n, f, segments=list(zip(cuts[:-1], cuts[1:])))[0]
+
+
+def route_scratch(S, n, K, P, device):
+    """The buffers one (S, n, K, P) routing call writes: thresholds, tile_comp, perm, zp, labels (callers cache them)."""
+    tiles = route_tiles(n, K, P)
+    if tiles < 1:
+        raise GwtfError(f'no routed layout for S={S}, n={n}, K={K}, P={P}')
+    i32 = dict(device=device, dtype=torch.int32)
+    return {'P': P, 'tiles': tiles, 'thresholds': torch.zeros(S, K, **i32), 'tile_comp': torch.empty(S, tiles, **i32),
+            'perm': torch.empty(S, tiles * P, **i32), 'zp': torch.empty(S, 3, tiles * P, device=device, dtype=torch.float32),
+            'labels': torch.empty(S, n, **i32)}
+
+
+def _explicit(t, name, shape, dtype, device):
+    if t is None:
+        return None
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise GwtfError(f'{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}')
+    return t.data_ptr()
+
+
+def mixture_route(work, logits=None, mu0=None, lv0=None, state=None, words=None, labels_in=None, normals=None, z0_in=None):
+    """gwtf_mixture_route on the current stream into the buffers of `work` (route_scratch).  logits (S, K) float32; mu0 / lv0 (S, 3) or
+    (1, 3) float32 (one row: shared by all shapes); state: clouds.make_state; the other four: the explicit draws of include/gwtf.h."""
+    S, n = work['labels'].shape
+    K, dev = work['thresholds'].shape[1], work['labels'].device
+    if state is not None and (state.dtype != torch.int64 or state.numel() != 2 or state.device != dev):
+        raise GwtfError('state must come from make_state(seed, device) on the device of the call')
+    f32, i32 = torch.float32, torch.int32
+    base = []
+    for t, name in ((mu0, 'mu0'), (lv0, 'lv0')):
+        if t is not None and (t.dim() != 2 or t.shape[0] not in (1, S) or t.shape[1] != 3):
+            raise GwtfError(f'{name} must be (S, 3) or (1, 3), got {tuple(t.shape)}')
+        base.append((_ptr(t, name), 0 if t is None or t.shape[0] == 1 else 3))
+    a = RouteArgs(logits=_explicit(logits, 'logits', (S, K), f32, dev), mu0=base[0][0], lv0=base[1][0],
+                  state=None if state is None else state.data_ptr(), words=_explicit(words, 'words', (S, n), i32, dev),
+                  labels_in=_explicit(labels_in, 'labels_in', (S, n), i32, dev), normals=_explicit(normals, 'normals', (S, 3, n), f32, dev),
+                  z0_in=_explicit(z0_in, 'z0_in', (S, 3, n), f32, dev), thresholds=work['thresholds'].data_ptr(),
+                  tile_comp=work['tile_comp'].data_ptr(), perm=work['perm'].data_ptr(), zp=work['zp'].data_ptr(),
+                  labels=work['labels'].data_ptr(), S=S, n=n, K=K, P=work['P'], mu0_stride=base[0][1], lv0_stride=base[1][1],
+                  stream=torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        check(lib().gwtf_mixture_route(ctypes.addressof(a)))
+    return work
+
+
+def stack_forward_routed(work, packed_w, film, out, logdet, K, C, f, pattern0, eps):
+    """gwtf_stack_forward_routed on the current stream: the layout in `work` through the K stacks -> out / logdet (S, 3, n) (logdet may
+    be None).  There is no exact body behind this launch."""
+    if EXACT[0]:
+        raise GwtfError('exact_fp32: the routed stack launch has no exact-fp32 body')
+    S, n = work['labels'].shape
+    if film.shape[0] != S or film.shape[1] != K * C:
+        raise GwtfError(f'film is {tuple(film.shape)}, expected ({S},{K * C},...)')
+    for t, name in ((out, 'out'), (logdet, 'logdet')):
+        if t is not None and tuple(t.shape) != (S, 3, n):
+            raise GwtfError(f'{name} is {tuple(t.shape)}, expected {(S, 3, n)}')
+    a = RoutedStackArgs(zp=work['zp'].data_ptr(), weights=_ptr(packed_w, 'packed_w'), film=_ptr(film, 'film'),
+                        tile_comp=work['tile_comp'].data_ptr(), perm=work['perm'].data_ptr(), out=_ptr(out, 'out'),
+                        logdet=_ptr(logdet, 'logdet'), K=K, S=S, n=n, P=work['P'], C=C, f=f, pattern0=pattern0, tune=_TUNE[0],
+                        eps=float(eps), stream=_stream(out))
+    with torch.cuda.device(out.device):
+        check(lib().gwtf_stack_forward_routed(ctypes.addressof(a)))
+    return out, logdet

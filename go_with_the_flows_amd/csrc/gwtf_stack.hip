@@ -539,9 +539,17 @@ struct Extras {
   size_t moments_stride_k;       // component k accumulates into moments_out + k * moments_stride_k
   int tpw;                       // one-coupling launches: consecutive tiles of ONE shape a workgroup walks (0 / 1 = one tile)
   int* worklist;                 // null, or the flagged-wave list the exact re-run launch reads (GwtfStackArgs.worklist)
+  // ROUTED instantiations only (gwtf_stack_forward_routed; every other launch leaves them zero and never reads them)
+  const int* tile_comp;          // [B][r_tiles] component of each tile slot, -1: unused
+  const int* perm;               // [B][r_tiles * 64 NB] original point index of each slot, -1: padding
+  int r_tiles, r_n;              // tile slots per shape; points per shape of out / logdet ([B][3][r_n])
 };
 
-template <int MB, int NB, int MODE, bool LISTS, int NJL = 0>
+// ROUTED (DIRECT, no lists; gwtf_mixture_route's layout, include/gwtf.h): tile slot (b, t) of the fixed r_tiles per shape runs
+// component tile_comp[b][t] on the 64 NB contiguous slots of `p` = zp [B][3][r_tiles * 64 NB] and stores every point at its original
+// index perm[b][slot] of out / logdet [B][3][r_n].  A slot nobody uses (-1) leaves before it stages anything: the grid is sized for
+// the worst split of the points over the components and most launches use all but a few of its slots.
+template <int MB, int NB, int MODE, bool LISTS, int NJL = 0, bool ROUTED = false>
 __global__ __launch_bounds__(256) void stack_kernel(const float* __restrict__ p, const float* __restrict__ pw,
                                                     const float* __restrict__ film, float* __restrict__ out,
                                                     float* __restrict__ logdet, float* __restrict__ ps,
@@ -570,15 +578,20 @@ __global__ __launch_bounds__(256) void stack_kernel(const float* __restrict__ p,
     bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
   }
   int comp = 0;
-  while (comp + 1 < jobs.K && bid >= jobs.tiles_cum[comp + 1]) ++comp;
-  const int n_begin = jobs.begin[comp], n_end = jobs.end[comp];
-  const int tiles_per_shape = (n_end - n_begin + 64 * NB - 1) / (64 * NB);
+  if constexpr (ROUTED) {
+    comp = ex.tile_comp[bid];
+    if (comp < 0 || comp >= jobs.K) return;                   // unused slot (or a table that is not the routing launch's)
+  } else {
+    while (comp + 1 < jobs.K && bid >= jobs.tiles_cum[comp + 1]) ++comp;
+  }
+  const int n_begin = ROUTED ? 0 : jobs.begin[comp], n_end = ROUTED ? N : jobs.end[comp];
+  const int tiles_per_shape = ROUTED ? ex.r_tiles : (n_end - n_begin + 64 * NB - 1) / (64 * NB);
   // One-coupling launches of the train pipeline (ex.tpw > 1): a workgroup walks tpw consecutive tiles of ONE shape, so the
   // coupling's weights and the shape's FiLM record are staged once per workgroup instead of once per tile -- such a launch is
   // 45 % prologue (31 us against a 14 us serial-sum floor, docs/LOG.md).  Whole-stack launches: one tile per workgroup.
   const int tpw = ex.tpw > 1 ? ex.tpw : 1;
   const int groups = (tiles_per_shape + tpw - 1) / tpw;
-  const int local = bid - jobs.tiles_cum[comp];
+  const int local = ROUTED ? bid : bid - jobs.tiles_cum[comp];
   const int b = local / groups;
   const int tile0 = (local - b * groups) * tpw;
   const int own_nb = q & (NB - 1);
@@ -727,7 +740,17 @@ __global__ __launch_bounds__(256) void stack_kernel(const float* __restrict__ p,
       if (lvs) lvs[o] = lv_last[d];
     }
   }
-  if (own_valid) {
+  if constexpr (ROUTED) {
+    const int dst = ex.perm[(size_t)b * N + n_own];            // every slot lies inside zp's row: N = r_tiles * 64 NB
+    if (own_valid && (unsigned)dst < (unsigned)ex.r_n) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const size_t o = ((size_t)b * 3 + d) * ex.r_n + dst;
+        out[o] = xo[d];
+        if (logdet) logdet[o] = ld[d];
+      }
+    }
+  } else if (own_valid) {
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
       const size_t o = ((size_t)b * 3 + d) * N + n_own;
@@ -904,6 +927,70 @@ static int stack_dispatch(const GwtfStackArgs* args, const Extras& ex_in) {
 extern "C" int gwtf_stack_forward(const GwtfStackArgs* args) {
   const Extras ex = {0, 0, nullptr, nullptr, 0, 0, args ? args->worklist : nullptr};
   return stack_dispatch(args, ex);
+}
+
+namespace {
+template <int MB, int NB>
+int launch_routed(const GwtfRoutedStackArgs& a, int tiles, int kk_steps, bool pipe) {
+  Jobs jobs = {};
+  jobs.K = a.K;                       // FiLM records per shape; the tile list itself is on the device (tile_comp)
+  Extras ex = {};
+  ex.tpw = 1;
+  ex.tile_comp = a.tile_comp;
+  ex.perm = a.perm;
+  ex.r_tiles = tiles;
+  ex.r_n = a.n;
+  const dim3 grid((unsigned)((long)a.S * tiles)), block(256);
+  auto run = [&](auto NJL_) {
+    hipLaunchKernelGGL((stack_kernel<MB, NB, GWTF_MODE_DIRECT, false, decltype(NJL_)::value, true>), grid, block, 0,
+                       (hipStream_t)a.stream, a.zp, a.weights, a.film, a.out, a.logdet, (float*)nullptr, (float*)nullptr,
+                       (float*)nullptr, a.S, tiles * 64 * NB, a.C, a.pattern0, a.eps, kk_steps, jobs, (size_t)0, (size_t)0, ex);
+    return (int)hipGetLastError();
+  };
+  const int njl = kk_steps - 8 * (Cfg<MB>::KS - 1);          // the same body choice as launch<MB, NB>
+  if (pipe) {
+    if constexpr (MB == 4 && NB <= 2) { if (njl == 8) return run(std::integral_constant<int, 8>{}); }
+    if constexpr (MB == 3) {
+      if (njl == 2) return run(std::integral_constant<int, 2>{});
+      if (njl == 1) return run(std::integral_constant<int, 1>{});
+    }
+    if constexpr (MB == 2) { if (njl == 5) return run(std::integral_constant<int, 5>{}); }
+  }
+  return run(std::integral_constant<int, 0>{});
+}
+template <int MB>
+int launch_routed_nb(int nb, const GwtfRoutedStackArgs& a, int tiles, int kk_steps, bool pipe) {
+  if (nb == 1) return launch_routed<MB, 1>(a, tiles, kk_steps, pipe);
+  if (nb == 2) return launch_routed<MB, 2>(a, tiles, kk_steps, pipe);
+  if constexpr (MB <= 4) return launch_routed<MB, 4>(a, tiles, kk_steps, pipe);
+  return GWTF_E_UNSUPPORTED;           // f > 64 keeps its accumulators in registers with at most 32 points per wave
+}
+}  // namespace
+
+// see include/gwtf.h
+extern "C" int gwtf_stack_forward_routed(const GwtfRoutedStackArgs* args) {
+  if (!args) return GWTF_E_BADARG;
+  const GwtfRoutedStackArgs& a = *args;
+  if (!a.zp || !a.weights || !a.film || !a.tile_comp || !a.perm || !a.out) return GWTF_E_BADARG;
+  if (a.K < 1 || a.K > GWTF_MAX_COMPONENTS || a.S < 1 || a.n < 1 || a.C < 1 || a.pattern0 < 0 || a.pattern0 > 5) return GWTF_E_BADARG;
+  if (a.P != 64 && a.P != 128 && a.P != 256) return GWTF_E_BADARG;
+  if (a.f < 1) return GWTF_E_BADARG;
+  if (a.f > GWTF_MAX_FP || (a.f > 64 && a.P > 128)) return GWTF_E_UNSUPPORTED;
+  const int tiles = gwtf_route_tiles(a.n, a.K, a.P);
+  if (tiles < 1 || (long)a.S * tiles > 0x7fffffffL / a.P) return GWTF_E_BADARG;      // slot indices are ints
+  const bool pipe = !(a.tune & GWTF_TUNE_GENERIC_BODY);
+  const int kk_steps = (a.f + 3) / 4, nb = a.P / 64;
+  switch (gwtf_padded_width(a.f) / 16) {
+    case 1: return launch_routed_nb<1>(nb, a, tiles, kk_steps, pipe);
+    case 2: return launch_routed_nb<2>(nb, a, tiles, kk_steps, pipe);
+    case 3: return launch_routed_nb<3>(nb, a, tiles, kk_steps, pipe);
+    case 4: return launch_routed_nb<4>(nb, a, tiles, kk_steps, pipe);
+    case 5: return launch_routed_nb<5>(nb, a, tiles, kk_steps, pipe);
+    case 6: return launch_routed_nb<6>(nb, a, tiles, kk_steps, pipe);
+    case 7: return launch_routed_nb<7>(nb, a, tiles, kk_steps, pipe);
+    case 8: return launch_routed_nb<8>(nb, a, tiles, kk_steps, pipe);
+    default: return GWTF_E_BADARG;
+  }
 }
 
 // One coupling of K stacks in one launch (K-batched train pipeline, gwtf_train.hip; gwtf_device.h)

@@ -231,6 +231,28 @@ def generation_metrics(sample_pcs, ref_pcs, f1_threshold_lst=(0.001,), cd_option
     return per_thr
 
 
+@torch.no_grad()
+def generate_clouds(model, n_shapes, n_points, batch_size=64, state=None):
+    """The generated set of the generation evaluation (evaluating.py:191-205: one `model(...)` call per shape in 'generating' mode) in
+    batches on the device: `encode` draws the latent codes from the learned prior (torch's generator of the device) and
+    `Flow_Mixture_Model.generate_many` turns them into clouds, components and base samples drawn from `state` (clouds.make_state;
+    None: the state the model keeps).  Nothing is read back between the batches.
+    -> (n_shapes, n_points, 3) float32, contiguous, on the model's device: the layout generation_metrics takes.
+    Unlike the reference's loop (evaluating.py:198-203) a cloud that holds NaN is NOT drawn again: looking for one is a host
+    synchronisation per batch.  Check `torch.isfinite(clouds).all()` once at the end if the model may diverge."""
+    if getattr(model, 'mode', None) != 'generating':
+        raise GwtfError("generate_clouds needs a model in 'generating' mode (model.mode / util_mode)")
+    if n_shapes < 1 or n_points < 1 or batch_size < 1:
+        raise ValueError('n_shapes, n_points and batch_size must be positive')
+    dev = next(model.parameters()).device
+    out = torch.empty(n_shapes, n_points, 3, device=dev, dtype=torch.float32)
+    for lo in range(0, n_shapes, batch_size):
+        bs = min(batch_size, n_shapes - lo)
+        g = model.encode(torch.empty(bs, 0, device=dev))['g_prior_samples'][-1]
+        out[lo:lo + bs] = model.generate_many(g, n_points, state=state).transpose(1, 2)
+    return out
+
+
 def pairwise_CD(clouds1, clouds2, bs=2048):
     """Chamfer distance (sum of the two directed means) of every cloud of ``clouds1`` against every cloud of ``clouds2``
     (reference utils.py:90-117) -> (N1, N2) float32 on the device.  ``bs`` (the reference's chunk size) is accepted and ignored:

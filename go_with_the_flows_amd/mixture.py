@@ -121,6 +121,53 @@ class MixtureStack:
         return _lib.stack_forward_multi(p.contiguous().float(), pw, film, self.K, self.C, self.f, e0.pattern0, eps, mode,
                                         segments=segs, shared_points=False, packed_x=px)
 
+    def _routed_work(self, S, n, device):
+        """The routing scratch of (S, n, K, P), P from the stack's tile choice under the current tuning word: allocated once."""
+        P = _lib.route_points_per_tile(S, n, self.K, self.f)
+        if not hasattr(self, '_route_work'):
+            self._route_work = {}
+        key = (S, n, self.K, P, str(device))
+        if key not in self._route_work:
+            self._route_work[key] = _lib.route_scratch(S, n, self.K, P, device)
+        return self._route_work[key]
+
+    def _routed_ready(self, g):
+        """What both routed entry points check before anything is launched."""
+        e0 = self.engines[0]
+        if e0.couplings[0].training:
+            raise NotImplementedError('the sampling partition is an evaluation path (reference flow_mixture.py:146); call .eval()')
+        if _lib.EXACT[0]:
+            raise _lib.GwtfError('exact_fp32: the routed stack launch has no exact-fp32 body')
+        return e0
+
+    def launch_routed(self, work, g, out=None, want_logdet=False):
+        """FiLM + the routed stack launch on a layout `_lib.mixture_route` left in `work` -> (out, logdet or None), each (S, 3, n)."""
+        e0 = self._routed_ready(g)
+        S, n = work['labels'].shape
+        if out is None:
+            out = torch.empty(S, 3, n, device=g.device, dtype=torch.float32)
+        logdet = torch.empty(S, 3, n, device=g.device, dtype=torch.float32) if want_logdet else None
+        pw, film, eps = self._film(g.contiguous().float())
+        return _lib.stack_forward_routed(work, pw, film, out, logdet, self.K, self.C, self.f, e0.pattern0, eps)
+
+    def forward_routed(self, z0, g, labels):
+        """Sampling path with per-point components: z0 (S,3,n) float32 base samples and labels (S,n) int32 in [0, K), both on the
+        device; point i of shape s goes through component labels[s, i] and comes back in its own position.  -> (out, logdet), each
+        (S,3,n).  Nothing is read back: the tile layout is built on the device (csrc/gwtf_route.hip).  A point that leaves the
+        f16-safe range comes back NaN, as from forward_partition."""
+        e0 = self._routed_ready(g)
+        e0._check(z0, g)
+        S, _, n = z0.shape
+        dev = z0.device
+        if not torch.is_tensor(labels) or labels.dtype != torch.int32 or labels.device != dev or tuple(labels.shape) != (S, n) \
+                or not labels.is_contiguous():
+            raise _lib.GwtfError(f'labels must be a contiguous int32 tensor of shape {(S, n)} on {dev}')
+        if z0.dtype != torch.float32 or not z0.is_contiguous():
+            raise _lib.GwtfError('z0 must be contiguous float32')
+        work = self._routed_work(S, n, dev)
+        _lib.mixture_route(work, labels_in=labels, z0_in=z0)
+        return self.launch_routed(work, g, want_logdet=True)
+
 
 class _MixtureNLLFn(torch.autograd.Function):
     @staticmethod

@@ -22,6 +22,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import _lib
+from ._lib import GwtfError
+from .clouds import make_state
 from .decoders import LocalCondRNVPDecoder
 from .encoders import FeatureEncoder, PointNetCloudEncoder, WeightsEncoder
 from .mixture import MixtureStack, flow_mixture_nll
@@ -385,6 +388,44 @@ class Flow_Mixture_Model(Local_Cond_RNVP_MC_Global_RNVP_VAE):
             return x, torch.from_numpy(labels + 1).to(x.device).float()
         return x
 
+    @torch.no_grad()
+    def generate_many(self, g_samples, n_points, return_labels=False, state=None, explicit=None, out=None):
+        """Generation for S shapes with NO host round trip between the latent codes and the clouds: the mixture logits, the base
+        Gaussian and the FiLM records stay on the device, one routing launch draws every point's component and base sample (Philox,
+        clouds.make_state's (seed, call) record, which the launch advances) and lays the points out in tiles of their components,
+        one routed stack launch sends every point through its own component (csrc/gwtf_route.hip, gwtf_stack.hip ROUTED).
+        -> (S, 3, n_points)[, labels (S, n_points) in 1..K as float].  state=None: a state the model keeps (seed 0).
+        explicit: {'words' (S,n) int32 bits | 'labels_in' (S,n) int32 in [0,K), 'normals' | 'z0_in' (S,3,n) float32} replaces the
+        draws (include/gwtf.h).  out: the result tensor.  After one eager call the same call can be captured in a graph: every
+        replay draws fresh clouds.  sample_many keeps the reference's np.random draws; this path has its own random stream."""
+        S, K = g_samples.shape[0], self.n_components
+        n, dev = int(n_points), g_samples.device
+        stack = self.mixture_stack()
+        stack._routed_ready(g_samples)
+        if dev.type != 'cuda':
+            raise GwtfError(f'g_samples lives on {dev}: generation runs on a HIP device only, there is no CPU path')
+        if out is None:
+            out = torch.empty(S, 3, n, device=dev, dtype=torch.float32)
+        elif tuple(out.shape) != (S, 3, n) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise GwtfError(f'out must be a contiguous float32 tensor of shape {(S, 3, n)} on {dev}')
+        if state is None:
+            if getattr(self, '_generate_state', None) is None or self._generate_state.device != dev:
+                self._generate_state = make_state(0, dev)
+            state = self._generate_state
+        ex = dict(explicit or {})
+        unknown = set(ex) - {'words', 'labels_in', 'normals', 'z0_in'}
+        if unknown:
+            raise GwtfError(f'explicit: unknown keys {sorted(unknown)}')
+        logits = self.get_weights(g_samples).contiguous().float()
+        mu0, lv0 = self._base_gaussian(g_samples)
+        work = stack._routed_work(S, n, dev)
+        _lib.mixture_route(work, logits=logits, mu0=mu0[:, :, 0].contiguous().float(), lv0=lv0[:, :, 0].contiguous().float(),
+                           state=state, **ex)
+        stack.launch_routed(work, g_samples, out=out)
+        if return_labels:
+            return out, (work['labels'] + 1).float()
+        return out
+
     def _decode_partitioned_many(self, z0, g_samples, labels):
         """z0 (S, 3, n) base samples, labels (S, n) numpy: point i of sample s through component labels[s, i] -> (S, 3, n)."""
         S, _, n = z0.shape
@@ -464,13 +505,17 @@ class Flow_Mixture_SVR_Model(Flow_Mixture_Model):
         raise NotImplementedError('Flow_Mixture_SVR_Model trains through forward + Flow_Mixture_Loss (the list path)')
 
     @torch.no_grad()
-    def reconstruct_many(self, images, n_points, return_labels=False):
+    def reconstruct_many(self, images, n_points, return_labels=False, state=None):
         """S images -> S clouds (the reference reconstructs one image per call, evaluating.py:94-96): the image encoder on all S
         (HIP in eval mode), the g0_prior means through the prior flow direct, then ``sample_many``'s partitioned decoder launch.
         Component draws are taken sample by sample (np.random.choice), in the order S calls of ``forward`` with B = 1 take them.
+        With a state (clouds.make_state) the decoder step is ``generate_many`` instead: components and base samples drawn on the
+        device from that state, no host round trip.
         -> (S, 3, n_points)[, labels (S, n_points) in 1..K]."""
         mus, _ = self.g0_prior(self.img_encoder(images))
         g = self.g_prior(mus, mode='direct')[0][-1]
+        if state is not None:
+            return self.generate_many(g, n_points, return_labels, state=state)
         return self.sample_many(g, n_points, return_labels)
 
 

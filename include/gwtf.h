@@ -583,6 +583,75 @@ int gwtf_cloud_partials(int M);
  * <= 0 where enabled, explicit draws given in part (reference cloud_sampling.py:4-32). */
 int gwtf_sample_clouds(const GwtfCloudArgs* args);
 
+/* Device-resident generation (ABI 10 gained these entry points; no existing record or signature changed): every point of S generated
+ * clouds draws its mixture component and its base sample on the device and is laid out so that ONE stack launch sends it through its
+ * own component -- the sampling branch of Flow_Mixture_Model.decode (lib/networks/flow_mixture.py:146-177: np.random.choice over the
+ * normalised weights, reparameterize of models.py:99-109, the K decoder passes, the scatter by mask) without a host round trip.
+ *
+ * gwtf_mixture_route (csrc/gwtf_route.hip): one workgroup per shape, then a one-thread launch that stores call + 1 into state[1].
+ *   Thresholds of shape s from its K float32 logits, in float64: e_k = exp(l_k - max l), cdf = cumsum(e),
+ *   T[k] = min(ceil(cdf[k] / cdf[K-1] * 2^32), 2^32 - 1) -- RandomState.choice's cdf and searchsorted(cdf, w 2^-32, 'right') at 32-bit
+ *   resolution, the construction of the cloud sampler's face thresholds.  Component of point i: #{k < K-1 : T[k] <= w_i}.
+ *   Base sample: z = eps * expf(0.5f * lv0) + mu0 per coordinate, float32, uncontracted; mu0 / lv0 of shape s are the three floats at
+ *   mu0 + s * mu0_stride (stride 0: one base Gaussian for all shapes).
+ *   Randomness: Philox4x32-10, key (seed lo, seed hi), counter (i, s, call lo, call hi | stream << 28), call < 2^60, with the streams
+ *   the cloud sampler leaves free: stream 2 gives w_i = word 0; stream 3 Box-Muller normals from (word 0, word 1) -> eps 0, eps 1 and
+ *   (word 2, word 3) -> eps 2.  Explicit draws replace either stream: labels_in (taken as they are, clamped to [0, K); no thresholds
+ *   are built) or words; z0_in (the base samples themselves) or normals.  state may be NULL when neither stream is drawn.
+ *   Layout, P = points per tile of the stack launch (64, 128 or 256): a shape owns tiles = gwtf_route_tiles(n, K, P) =
+ *   floor((n + K (P - 1)) / P) tile slots, an upper bound of sum_k ceil(c_k / P) for any counts c_k that sum to n; component k takes
+ *   ceil(c_k / P) consecutive slots, in component order, its points in their original order (a stable counting sort: the outputs are a
+ *   function of the labels alone and bit-reproducible -- no atomics on global memory).
+ *     tile_comp [S][tiles]        component of each slot, -1: unused
+ *     perm      [S][tiles * P]    original index of the point in each position, -1: padding
+ *     zp        [S][3][tiles * P] base samples in that order, padding 0
+ *     labels    [S][n]            component of each point
+ *     thresholds [S][K]           the bits of the uint32 thresholds (may be NULL; not written with labels_in)
+ * gwtf_stack_forward_routed (csrc/gwtf_stack.hip): the split-f16 stack, DIRECT, on that layout -- slot (s, t) runs component
+ *   tile_comp[s][t] on its P positions of zp and stores each point at perm's index of out / logdet [S][3][n] (logdet may be NULL);
+ *   unused slots exit at once.  weights / film as for gwtf_stack_forward with K components; P must be the routing call's (f > 64:
+ *   P <= 128, else GWTF_E_UNSUPPORTED).  No work list and no exact re-run: a point that leaves the f16-safe range comes back NaN.
+ *   tune: GWTF_TUNE_GENERIC_BODY only (the caller chooses P, e.g. from gwtf_stack_plan over K equal segments). */
+typedef struct GwtfRouteArgs {
+  const float* logits;               /* [S][K]; NULL with labels_in */
+  const float* mu0;                  /* base mean / log-variance; NULL with z0_in */
+  const float* lv0;
+  long long* state;                  /* {seed, call} */
+  const int* words;                  /* explicit: [S][n] bits of the uint32 label words, or NULL */
+  const int* labels_in;              /* explicit: [S][n] components; takes precedence over words */
+  const float* normals;              /* explicit: [S][3][n] standard normals, or NULL */
+  const float* z0_in;                /* explicit: [S][3][n] base samples; takes precedence over normals */
+  int* thresholds;
+  int* tile_comp;
+  int* perm;
+  float* zp;
+  int* labels;
+  int S, n, K, P;
+  int mu0_stride, lv0_stride;        /* floats from one shape's values to the next: 3, or 0 for shared values */
+  void* stream;
+} GwtfRouteArgs;
+typedef struct GwtfRoutedStackArgs {
+  const float* zp;
+  const float* weights;              /* [K][C][gwtf_packed_w_coupling_floats] */
+  const float* film;                 /* [S][K*C][gwtf_film_out_floats] */
+  const int* tile_comp;
+  const int* perm;
+  float* out;                        /* [S][3][n] */
+  float* logdet;                     /* [S][3][n] or NULL */
+  int K, S, n, P, C, f;
+  int pattern0;
+  int tune;
+  float eps;
+  void* stream;
+} GwtfRoutedStackArgs;
+/* Tile slots per shape of the routed layout; 0 for arguments the two entry points reject.  Host only. */
+int gwtf_route_tiles(int n, int K, int P);
+/* Both return GWTF_E_BADARG without a launch for a NULL record or required pointer, K outside 1..64, S < 1, n < 1, P not in
+ * {64, 128, 256}, a draw that is neither explicit nor given a state; the stack launch GWTF_E_UNSUPPORTED for a width outside 1..128
+ * or P = 256 beyond f = 64. */
+int gwtf_mixture_route(const GwtfRouteArgs* args);
+int gwtf_stack_forward_routed(const GwtfRoutedStackArgs* args);
+
 #ifdef __cplusplus
 }
 #endif
