@@ -506,10 +506,3 @@ def train_density_forward_multi(engines, p, g, mode='inverse', distributed=False
     bn_batch[:, :, :, 2:4, 0] = film_mean.view(K, C, 2, 2, f)
     bn_batch[:, :, :, 2:4, 1] = film_var.view(K, C, 2, 2, f)
     return out, logdet, lists, bn_batch
-
-
-def train_density_forward_fast(engine, p, g, mode='inverse', distributed=False, want_lists=True):
-    """One stack through the fused pipeline.  -> out, logdet (B,3,N), lists = (ps, mus, lvs) (C,B,3,N) each (None unless
-    want_lists), bn_batch (C,2,4,2,f)."""
-    out, logdet, lists, bn_batch = train_density_forward_multi([engine], p, g, mode, distributed, want_lists)
-    return out[0], logdet[0], tuple(t[0] for t in lists) if want_lists else None, bn_batch[0]

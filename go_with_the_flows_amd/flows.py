@@ -183,34 +183,42 @@ class CondRealNVPFlow3DTriple(nn.Module):
         return self._engine.run_lists(p, g, mode)
 
 
-class _ArenaCat(torch.autograd.Function):
-    """raw arena = cat(flattened parameters / buffers) as ONE autograd node: forward concatenates cached detached views,
-    backward hands every parameter its slice of the flat gradient (views, no kernels)."""
+class _DeviceTable:
+    """Rows on the host, their table on the device.  The device tensor is kept while the rows are equal: building it is a
+    host-to-device copy, which is not allowed while a hipGraph is captured."""
 
-    @staticmethod
-    def forward(ctx, engine, *tensors):
-        ctx.engine = engine
-        return engine._cat_detached()
+    def __init__(self):
+        self.source = None                # what the owner derived `rows` from (compared by identity before deriving them again)
+        self.rows, self.table = None, None
 
-    @staticmethod
-    def backward(ctx, g_raw):
-        eng = ctx.engine
-        pieces = g_raw.split_with_sizes(eng._sizes)
-        grads, k = [], 0
-        for (t, op), piece in zip(eng._srcs, pieces):
-            if t is None:
-                continue
-            k += 1
-            if not ctx.needs_input_grad[k]:
-                grads.append(None)
-            else:
-                grads.append(piece.view(t.shape))
-        return (None, *grads)
+    def lookup(self, rows, device, dtype=torch.int64):
+        """The device tensor of `rows`: the cached one (the same object) while they are equal, else a new one -- or None while
+        the current stream is capturing: the caller takes its fallback, and the next call outside a capture builds the table."""
+        if self.table is None or self.table.device != device or (rows is not self.rows and rows != self.rows):
+            if device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+                return None
+            self.table = torch.tensor(rows, dtype=dtype).to(device)
+        self.rows = rows
+        return self.table
+
+
+def _needs_grad(p, g, engines):
+    """Whether a pass over these engines has to be differentiable (buffers never require grad: the cached tracked tensors
+    answer as the modules' parameters() would)."""
+    return torch.is_grad_enabled() and (p.requires_grad or g.requires_grad or
+                                        any(t.requires_grad for e in engines for t in e._tracked or e._collect()))
+
+
+def exact_record(stack, rerun=True):
+    """stack.packed_exact() where the launch takes it -- for the re-run of out-of-range tiles (range_rerun; rerun=False: a path
+    that does not re-run) or because the exact body is forced -- else None."""
+    return stack.packed_exact() if ((rerun and range_rerun()) or _lib.EXACT[0]) else None
 
 
 class _ArenaCatMulti(torch.autograd.Function):
-    """The raw arenas of K engines of one shape as ONE (K, R) tensor built by ONE pointer-table launch (a mixture's K decoders:
-    instead of K gathers and a torch.stack); backward hands every parameter its slice, like _ArenaCat."""
+    """The raw arenas of K engines of one shape as ONE (K, R) tensor and ONE autograd node: forward is ONE pointer-table launch
+    over cached detached views (a mixture's K decoders: instead of K gathers and a torch.stack), backward hands every parameter
+    its slice of the flat gradient (views, no kernels)."""
 
     @staticmethod
     def forward(ctx, engines, *tensors):
@@ -229,36 +237,32 @@ class _ArenaCatMulti(torch.autograd.Function):
 
 
 def _gather_stacked(engines):
-    """(K, R) stacked raw arena from the engines' cached detached views; the combined device table is cached per engine tuple and
-    rebuilt when a source pointer changed (not inside a hipGraph capture: per-engine gathers + torch.stack stand in there)."""
-    for e in engines:
-        e._refresh_flat()
-    flat0 = engines[0]._flat
-    R = sum(engines[0]._sizes)
-    if not flat0[0].is_cuda:
-        return torch.stack([torch.cat(e._flat) for e in engines])
+    """(K, R) stacked raw arena from the engines' cached detached views (refreshed by the caller): one pointer-table kernel
+    (csrc/gwtf_train.hip) on a HIP device -- torch.cat would be a launch per 128 inputs, eleven for an 11-Triple decoder.  The
+    device table is rebuilt only when a source pointer changed (not inside a hipGraph capture: torch.cat stands in there)."""
+    flats = [e._flat for e in engines]
+    dev = flats[0][0].device
+    if dev.type != 'cuda':
+        return torch.stack([torch.cat(flat) for flat in flats])
     # the combined table lives on the first engine (it dies with the model: a module-level cache keyed on id() would keep the
     # detached parameter views and the device table of every model ever built alive)
-    key = tuple(id(e) for e in engines)
-    tables = engines[0].__dict__.setdefault('_stack_tables', {})
-    tab = tables.get(key)
-    flats = [e._flat for e in engines]
-    if tab is None or len(tab[0]) != len(flats) or any(x is not y for x, y in zip(tab[0], flats)):   # a flat list is rebuilt with its tensors
+    tab = engines[0]._stack_tables.setdefault(tuple(id(e) for e in engines), _DeviceTable())
+    R = sum(engines[0]._sizes)
+    rows = tab.rows
+    if tab.source is None or any(x is not y for x, y in zip(tab.source, flats)):   # a flat list is rebuilt with its tensors
         rows = []
         for k, e in enumerate(engines):
             off = k * R
             for t, n in zip(e._flat, e._sizes):
                 rows.append((t.data_ptr(), off, n))
                 off += n
-        if tab is not None and tab[1] == rows:
-            tab = tables[key] = (flats, rows, tab[2])
-        elif torch.cuda.is_current_stream_capturing():
-            return torch.stack([e._cat_detached() for e in engines])
-        else:
-            tab = tables[key] = (flats, rows, torch.tensor(rows, dtype=torch.int64).to(flat0[0].device))
-    out = torch.empty(len(engines), R, device=flat0[0].device, dtype=torch.float32)
-    with torch.cuda.device(out.device):
-        _lib.check(_lib.lib().gwtf_gather_table(tab[2].data_ptr(), out.data_ptr(), len(tab[1]), _lib._stream(out)))
+    table = tab.lookup(rows, dev)
+    if table is None:
+        return torch.stack([torch.cat(flat) for flat in flats])
+    tab.source = flats                    # tab.rows describe these lists
+    out = torch.empty(len(engines), R, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().gwtf_gather_table(table.data_ptr(), out.data_ptr(), len(rows), _lib._stream(out)))
     return out
 
 
@@ -271,6 +275,16 @@ def stacked_raw_arena(engines):
     if torch.is_grad_enabled() and any(t.requires_grad for t in srcs):
         return _ArenaCatMulti.apply(engines, *srcs)
     return _gather_stacked(engines)
+
+
+class _BnTables:
+    """What StackEngine._update_running_stats keeps between calls: the rows of the tracked BatchNorm modules (derived per
+    stamp) and their device tables."""
+
+    def __init__(self):
+        self.stamp, self.n_mods, self.touched = None, 0, []     # touched: the buffers the update writes
+        self.ptr_rows, self.mom_rows, self.idx_rows = [], [], []  # per tracked module: buffer pointers, momentum, index in bn_batch
+        self.ptrs, self.momentum, self.index = _DeviceTable(), _DeviceTable(), _DeviceTable()
 
 
 class StackEngine:
@@ -294,9 +308,10 @@ class StackEngine:
         self._tracked, self._tracked_stamp = [], None
         self._srcs, self._src_stamp, self._zeros = None, None, None
         self._cache_key = None
-        self._packed = None
+        self._packed, self._packed_x = None, None
         self._flat_key, self._flat = None, None
-        self._bn_cache = None
+        self._stack_tables = {}           # engine tuple -> _DeviceTable of the gathers this engine leads (_gather_stacked)
+        self._bn = _BnTables()
 
     def __reduce__(self):
         """copy.deepcopy / pickle of a module that owns an engine: a FRESH engine over the (copied) couplings.  Every cache in
@@ -305,57 +320,31 @@ class StackEngine:
         return (StackEngine, (self.couplings,))
 
     def raw_arena(self):
-        """Parameters + BatchNorm buffers of all couplings as one flat tensor (autograd-aware torch.cat).  The list
-        of sources is cached (module traversal costs more than the copy); it is rebuilt when .to()/.cuda()/
-        load_state_dict() re-create tensors (stamp change)."""
-        self._refresh_flat()
-        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t, _ in self._srcs):
-            return _ArenaCat.apply(self, *[t for t, _ in self._srcs if t is not None])
-        return self._cat_detached()
+        """Parameters + BatchNorm buffers of all couplings as one flat tensor (autograd-aware: stacked_raw_arena of this engine
+        alone, as a view -- a select would add a zero-filled (1, R) gradient and a copy to the backward)."""
+        return stacked_raw_arena([self]).view(-1)
 
     def _refresh_flat(self):
-        """(Re)build the cached source list and its detached flat views."""
+        """(Re)build the cached source list and its detached flat views.  The list of sources is cached (module traversal costs
+        more than the copy); it is rebuilt when .to()/.cuda()/load_state_dict() re-create tensors (stamp change)."""
         stamp = sum(c._stamp for c in self.couplings)
         if stamp != self._src_stamp:
             self._srcs = [so for c in self.couplings for so in c.raw_sources()]
             dev = self.couplings[0].eps.device
-            self._zeros = {n: torch.zeros(n, device=dev) for n in {op for t, op in self._srcs if t is None}}
+            # (the padding tensors are kept while the device is: their pointers are rows of the gather table)
+            kept = {n: z for n, z in (self._zeros or {}).items() if z.device == dev}
+            self._zeros = {n: kept[n] if n in kept else torch.zeros(n, device=dev) for n in {op for t, op in self._srcs if t is None}}
             self._src_stamp = stamp
             self._flat_key = None
         # The 1320 flattened views (11-Triple decoder) are cached as DETACHED views: building them costs more host time
         # than the copy.  They must not carry autograd history -- a cached differentiable view of a parameter that the
         # optimiser then updates in place gets an AsStridedBackward grad_fn (new_zeros + copy per parameter, measured:
-        # +2000 kernels per step).  The autograd link is one custom node instead (_ArenaCat below).
+        # +2000 kernels per step).  The autograd link is one custom node instead (_ArenaCatMulti above).
         if self._flat_key is None:
             z = self._zeros
             self._flat = [z[op] if t is None else t.detach().view(-1) for t, op in self._srcs]
             self._sizes = [op if t is None else t.numel() for t, op in self._srcs]
             self._flat_key = True
-
-    def _cat_detached(self):
-        """The flat arena from the cached detached views: one pointer-table kernel (csrc/gwtf_train.hip) on a HIP device --
-        torch.cat would be a launch per 128 inputs, eleven for an 11-Triple decoder.  The device table is rebuilt only when a
-        source pointer changed (it is a host-to-device copy: not allowed inside a hipGraph capture, where torch.cat stands in)."""
-        flat = self._flat
-        if not flat[0].is_cuda:
-            return torch.cat(flat)
-        rows, off = [], 0
-        tab = getattr(self, '_gather_tab', None)
-        if tab is None or tab[0] is not flat:
-            for t, n in zip(flat, self._sizes):
-                rows.append((t.data_ptr(), off, n))
-                off += n
-            if tab is not None and tab[1] == rows:
-                tab = self._gather_tab = (flat, rows, tab[2], off)
-            elif torch.cuda.is_current_stream_capturing():
-                return torch.cat(flat)
-            else:
-                tab = self._gather_tab = (flat, rows, torch.tensor(rows, dtype=torch.int64).to(flat[0].device), off)
-        _, rows, table, total = tab
-        out = torch.empty(total, device=flat[0].device, dtype=torch.float32)
-        with torch.cuda.device(out.device):
-            _lib.check(_lib.lib().gwtf_gather_table(table.data_ptr(), out.data_ptr(), len(rows), _lib._stream(out)))
-        return out
 
     def _collect(self):
         self._key()
@@ -382,7 +371,7 @@ class StackEngine:
     def packed_exact(self):
         """The exact-fp32 operand record of the CURRENT eval packing (cached with it)."""
         pw, pf = self.packed()
-        if getattr(self, '_packed_x', None) is None:
+        if self._packed_x is None:
             with torch.no_grad():
                 self._packed_x = _lib.pack_weights_exact(self.raw_arena(), pf, self.C, self.f, self.G, self.pattern0)
         return self._packed_x
@@ -410,29 +399,31 @@ class StackEngine:
             B = p.shape[0]
             lists = p.new_zeros(3, self.C, B, 3, 0, dtype=torch.float32) if want_lists else None
             return p.new_zeros(B, 3, 0, dtype=torch.float32), p.new_zeros(B, 3, 0, dtype=torch.float32), lists
-        needs_grad = torch.is_grad_enabled() and (p.requires_grad or g.requires_grad or
-                                                  any(t.requires_grad for t in self._tracked or self._collect()))
+        needs_grad = _needs_grad(p, g, [self])
         if (needs_grad or c0.training) and self.f > 96:
             raise NotImplementedError(f'f_n_features={self.f}: train-mode BatchNorm and the backward pass are built for widths up to '
                                       '96 (their LDS working set exceeds 160 KiB beyond); eval-mode forward works up to 128')
         if c0.training:
             # batch-statistic BatchNorm, with or without autograd, one rank or several: the fused pipeline (autograd.py
             # TrainMixtureFn; several ranks all-reduce one packed statistic per phase, as SyncBatchNorm does, train_ae.py:152)
-            from .autograd import train_density_forward_fast
-            out, logdet, lists, bn_batch = train_density_forward_fast(self, p, g, mode, distributed=_sharded(), want_lists=want_lists)
-            self._update_running_stats(bn_batch)
-            return out, logdet, lists
+            from .autograd import train_density_forward_multi
+            out, logdet, lists, bn_batch = train_density_forward_multi([self], p, g, mode, distributed=_sharded(), want_lists=want_lists)
+            self._update_running_stats(bn_batch[0])
+            return out[0], logdet[0], tuple(t[0] for t in lists) if want_lists else None
         if needs_grad:
             # differentiable density pass: HIP forward + HIP backward (autograd.py); every ps[j] / logvars[j] list entry is
             # differentiable as in the reference (decoders.py:61-79); a gradient through a mus[j] entry raises
             from .autograd import density_forward
             return density_forward(self, p, g, mode)
-        pc, gc = p.contiguous().float(), g.contiguous().float()
-        eps = c0._eps_value
+        pw, film, eps = self._film(g.contiguous().float())
+        return _lib.stack_forward(p.contiguous().float(), pw, film, self.C, self.f, self.pattern0, eps, mode, want_lists,
+                                  packed_x=exact_record(self))
+
+    def _film(self, g):
+        """-> (packed stack weights, FiLM record of g, eps): what a stack launch on the current eval packing takes."""
         pw, pf = self.packed()
-        px = self.packed_exact() if (range_rerun() or _lib.EXACT[0]) else None
-        film = _lib.film_forward(gc, pf, self.C, self.f, eps)
-        return _lib.stack_forward(pc, pw, film, self.C, self.f, self.pattern0, eps, mode, want_lists, packed_x=px)
+        eps = self.couplings[0]._eps_value
+        return pw, _lib.film_forward(g, pf, self.C, self.f, eps), eps
 
     # -- train mode: batch-statistic BatchNorm ----------------------------------------------------------
     def _bn_modules(self):
@@ -446,56 +437,49 @@ class StackEngine:
 
     def _update_running_stats(self, bn_batch):
         """running = (1-m)*running + m*batch with the unbiased batch variance (torch.nn.BatchNorm1d semantics)."""
+        bn = self._bn
         stamp = sum(c._stamp for c in self.couplings)
-        capturing = bn_batch.is_cuda and torch.cuda.is_current_stream_capturing()
-        if self._bn_cache is None or self._bn_cache[0] != stamp or (self._bn_cache[2] is None and not capturing):
-            # (re)derive the pointer rows; the device table is rebuilt only when a pointer really changed (load_state_dict copies
-            # in place and keeps them), because building it is a host-to-device copy -- not allowed while a hipGraph is captured
+        if bn.stamp != stamp:
+            # (re)derive the rows; the device tables are rebuilt only when a pointer really changed (load_state_dict copies in
+            # place and keeps them), because building them is a host-to-device copy -- not allowed while a hipGraph is captured
             mods = self._bn_modules()
-            rows, moms, touched = [], [], []
+            ptr_rows, mom_rows, idx_rows, touched = [], [], [], []
             for i, m in enumerate(mods):
                 if m.track_running_stats and m.running_mean is not None:
                     if m.momentum is None:
                         raise NotImplementedError('BatchNorm momentum=None (cumulative average) is not supported by the fused '
                                                   'running-statistic update; the reference never sets it (flows.py:27-42)')
                     nbt = m.num_batches_tracked
-                    rows.append((i, m.running_mean.data_ptr(), m.running_var.data_ptr(), nbt.data_ptr() if nbt is not None else 0,
-                                 float(m.momentum)))
+                    idx_rows.append(i)
+                    mom_rows.append(float(m.momentum))
+                    ptr_rows.append((m.running_mean.data_ptr(), m.running_var.data_ptr(), nbt.data_ptr() if nbt is not None else 0))
                     touched += [m.running_mean, m.running_var] + ([nbt] if nbt is not None else [])
-            old = self._bn_cache
-            if old is not None and old[3] == rows and old[2] is not None and old[2][0] is not None and old[2][0].device == bn_batch.device:
-                self._bn_cache = (stamp, len(mods), old[2], rows, touched)
-            elif capturing:
-                # no device table can be built inside a capture (host-to-device copy): this capture takes the per-module route
-                # below; the next call outside a capture builds the table (the condition above)
-                self._bn_cache = (stamp, len(mods), None, rows, touched)
-            else:
-                dev = bn_batch.device
-                table = torch.tensor([r[1:4] for r in rows], dtype=torch.int64).to(dev) if rows else None
-                momentum = torch.tensor([r[4] for r in rows], dtype=torch.float32).to(dev) if rows else None
-                index = None if len(rows) == len(mods) else torch.tensor([r[0] for r in rows], dtype=torch.int64, device=dev)
-                self._bn_cache = (stamp, len(mods), (table, momentum, index), rows, touched)
-        _, n_mods, dev_tabs, rows, touched = self._bn_cache
-        if not rows:
+            bn.stamp, bn.n_mods, bn.touched = stamp, len(mods), touched
+            bn.ptr_rows, bn.mom_rows, bn.idx_rows = ptr_rows, mom_rows, idx_rows
+        if not bn.idx_rows:
             return
+        dev = bn_batch.device
+        table, momentum, index = (bn.ptrs.lookup(bn.ptr_rows, dev), bn.momentum.lookup(bn.mom_rows, dev, torch.float32),
+                                  bn.index.lookup(bn.idx_rows, dev))
         with torch.no_grad():
-            flat = bn_batch.reshape(n_mods, 2, self.f)
-            if dev_tabs is None:      # no device table yet (first call fell inside a graph capture): plain _foreach_ updates
+            flat = bn_batch.reshape(bn.n_mods, 2, self.f)
+            if table is None or momentum is None or index is None:
+                # no device table can be built inside a capture (host-to-device copy): this capture takes plain per-module
+                # updates; the next call outside a capture builds the tables
                 mods = self._bn_modules()
-                for i, _rm, _rv, _nbt, mom in rows:
+                for i, mom in zip(bn.idx_rows, bn.mom_rows):
                     mods[i].running_mean.mul_(1.0 - mom).add_(flat[i, 0], alpha=mom)
                     mods[i].running_var.mul_(1.0 - mom).add_(flat[i, 1], alpha=mom)
                     if mods[i].num_batches_tracked is not None:
                         mods[i].num_batches_tracked.add_(1)
                 return
-            table, momentum, index = dev_tabs
-            if index is not None:
+            if len(bn.idx_rows) < bn.n_mods:
                 flat = flat.index_select(0, index)
             flat = flat.contiguous()
             with torch.cuda.device(flat.device):
                 _lib.check(_lib.lib().gwtf_bn_running_update(table.data_ptr(), _lib._ptr(flat, 'bn_batch'), _lib._ptr(momentum, 'momentum'),
                                                             table.shape[0], self.f, _lib._stream(flat)))
-            torch._C._increment_version(touched)      # written through raw pointers: the packed-weight caches key on versions
+            torch._C._increment_version(bn.touched)      # written through raw pointers: the packed-weight caches key on versions
 
     def capture(self, p, g, mode, want_lists=False):
         """hipGraph capture of (FiLM + fused stack) on the CURRENT packed weights and on the storage of ``p``/``g``.
@@ -526,14 +510,13 @@ class GraphedStack:
         self.engines = list(engines)
         self.p, self.g, self.mode = p, g, mode
         packs = [e.packed() for e in self.engines]
-        pxs = [e.packed_exact() if (range_rerun() or _lib.EXACT[0]) else None for e in self.engines]
-        eps = self.engines[0].couplings[0]._eps_value
+        pxs = [exact_record(e) for e in self.engines]
         ps = per_engine_p if per_engine_p is not None else [p] * len(self.engines)
 
         def body():
             res = []
-            for e, (pw, pf), px, pk in zip(self.engines, packs, pxs, ps):
-                film = _lib.film_forward(g, pf, e.C, e.f, eps)
+            for e, px, pk in zip(self.engines, pxs, ps):
+                pw, film, eps = e._film(g)
                 res.append(_lib.stack_forward(pk, pw, film, e.C, e.f, e.pattern0, eps, mode, want_lists, packed_x=px))
             return res
 

@@ -9,6 +9,7 @@ all components, and one reduction kernel produces the per-shape NLL.
 import torch
 
 from . import _lib
+from .flows import _needs_grad, _sharded, exact_record
 
 
 class MixtureStack:
@@ -21,7 +22,10 @@ class MixtureStack:
         if any((e.C, e.f, e.G, e.pattern0) != (e0.C, e0.f, e0.G, e0.pattern0) for e in self.engines):
             raise ValueError('all mixture components must share n_flows, f_n_features and g_n_features')
         self.K, self.C, self.f, self.G = len(self.engines), e0.C, e0.f, e0.G
-        self._cat_key, self._cat = None, None
+        # concatenated packings, keyed on the engines' own (cached) tensors, which are kept alive beside them
+        self._cat_key, self._cat, self._keep = None, None, None
+        self._catx_key, self._catx, self._keepx = None, None, None
+        self._route_work = {}             # (S, n, K, P, device) -> routing scratch
 
     def __reduce__(self):
         """copy.deepcopy / pickle: a fresh stack over the (copied) decoders -- the caches here belong to the original's tensors."""
@@ -40,7 +44,7 @@ class MixtureStack:
         self.packed()
         pxs = [e.packed_exact() for e in self.engines]
         key = tuple(id(x) for x in pxs)
-        if key != getattr(self, '_catx_key', None):
+        if key != self._catx_key:
             # (each engine's record carries its own work list behind it, _lib.pack_weights_exact: the K record parts, then ONE list)
             n = self.C * _lib.lib().gwtf_packed_x_coupling_floats(self.f)
             tail = torch.zeros(_lib.WORKLIST_INTS, device=pxs[0].device, dtype=torch.float32)
@@ -56,17 +60,13 @@ class MixtureStack:
         """Every component on every point -> (out, logdet), each (K,B,3,N).  Training / density path."""
         e0 = self.engines[0]
         e0._check(p, g)
-        needs_grad = torch.is_grad_enabled() and (p.requires_grad or g.requires_grad or any(
-            t.requires_grad for d in self.decoders for t in d.parameters()))
+        needs_grad = _needs_grad(p, g, self.engines)
         if e0.couplings[0].training:
             # batch-statistic BatchNorm: all K components through every kernel of the train pipeline together
             # (csrc/gwtf_train.hip, K-batched pipeline); data-parallel runs all-reduce one packed statistic per phase
-            import torch.distributed as dist
             from .autograd import train_density_forward_multi
-            from .flows import _sharded
-            multi = _sharded()
             with torch.set_grad_enabled(needs_grad):
-                out, logdet, _, bn_batch = train_density_forward_multi(self.engines, p, g, mode, distributed=multi, want_lists=False)
+                out, logdet, _, bn_batch = train_density_forward_multi(self.engines, p, g, mode, distributed=_sharded(), want_lists=False)
             for k, e in enumerate(self.engines):
                 e._update_running_stats(bn_batch[k])
             return out, logdet
@@ -74,10 +74,9 @@ class MixtureStack:
             # eval BatchNorm with autograd: the per-component differentiable path
             res = [e.run(p, g, mode, False) for e in self.engines]
             return torch.stack([r[0] for r in res]), torch.stack([r[1] for r in res])
-        from .flows import range_rerun
         pw, film, eps = self._film(g.contiguous().float())
-        px = self.packed_exact() if (range_rerun() or _lib.EXACT[0]) else None
-        return _lib.stack_forward_multi(p.contiguous().float(), pw, film, self.K, self.C, self.f, e0.pattern0, eps, mode, packed_x=px)
+        return _lib.stack_forward_multi(p.contiguous().float(), pw, film, self.K, self.C, self.f, e0.pattern0, eps, mode,
+                                        packed_x=exact_record(self))
 
     def forward_all_lists(self, p, g, mode='inverse', defer_running_stats=False):
         """Every component on every point, train-mode BatchNorm, WITH the reference's per-coupling lists: -> (out, logdet (K,B,3,N),
@@ -90,9 +89,7 @@ class MixtureStack:
         if not e0.couplings[0].training:
             return None
         from .autograd import train_density_forward_multi
-        from .flows import _sharded
-        needs_grad = torch.is_grad_enabled() and (p.requires_grad or g.requires_grad or any(
-            t.requires_grad for d in self.decoders for t in d.parameters()))
+        needs_grad = _needs_grad(p, g, self.engines)
         with torch.set_grad_enabled(needs_grad):
             out, logdet, lists, bn_batch = train_density_forward_multi(self.engines, p, g, mode, distributed=_sharded())
         if defer_running_stats:
@@ -117,15 +114,12 @@ class MixtureStack:
             off += int(cnt)
         pw, film, eps = self._film(g.contiguous().float())
         # no re-run launch here (base samples of a few units; one shape per call is latency-bound) unless the exact body is forced
-        px = self.packed_exact() if _lib.EXACT[0] else None
         return _lib.stack_forward_multi(p.contiguous().float(), pw, film, self.K, self.C, self.f, e0.pattern0, eps, mode,
-                                        segments=segs, shared_points=False, packed_x=px)
+                                        segments=segs, shared_points=False, packed_x=exact_record(self, rerun=False))
 
     def _routed_work(self, S, n, device):
         """The routing scratch of (S, n, K, P), P from the stack's tile choice under the current tuning word: allocated once."""
         P = _lib.route_points_per_tile(S, n, self.K, self.f)
-        if not hasattr(self, '_route_work'):
-            self._route_work = {}
         key = (S, n, self.K, P, str(device))
         if key not in self._route_work:
             self._route_work[key] = _lib.route_scratch(S, n, self.K, P, device)
