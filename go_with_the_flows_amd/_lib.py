@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GWTF_LIB') or os.path.join(_HERE, 'libgwtf_hip.so')      # GWTF_LIB: an A/B build (tools/ab_build.sh)
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 MODE_DIRECT, MODE_INVERSE = 0, 1
 STAT_REPLICAS = 64   # GWTF_STAT_REPLICAS in csrc/gwtf_layout.h
@@ -67,20 +67,10 @@ _SIGNATURES = {
     'gwtf_enc_train_supported': (ctypes.c_int, [_c_fp, ctypes.c_int]),
     'gwtf_enc_train_units_floats': (ctypes.c_size_t, [ctypes.c_int]),
     'gwtf_enc_train_act_floats': (ctypes.c_size_t, [ctypes.c_int] * 3),
-    'gwtf_enc_train_pack_all': (ctypes.c_int, [_c_fp] * 10),
-    'gwtf_enc_train_xmoments': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_enc_train_fold0': (ctypes.c_int, [_c_fp, ctypes.c_double] + [_c_fp] * 5 + [ctypes.c_float, _c_fp, _c_fp, _c_fp]),
-    'gwtf_enc_train_fold': (ctypes.c_int, [_c_fp, ctypes.c_int, ctypes.c_double] + [_c_fp] * 4 + [ctypes.c_float, _c_fp, _c_fp, _c_fp]),
-    'gwtf_enc_train_forward': (ctypes.c_int, [ctypes.c_int] + [_c_fp] * 9 + [ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_enc_train_pool': (ctypes.c_int, [_c_fp] * 6 + [ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_enc_train_top_scatter': (ctypes.c_int, [_c_fp] * 7 + [ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_enc_train_backward_top': (ctypes.c_int, [_c_fp] * 10 + [ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_enc_train_top': (ctypes.c_int, [_c_fp] * 7 + [ctypes.c_int, _c_fp]),
-    'gwtf_enc_train_bwd_consts': (ctypes.c_int, [_c_fp, ctypes.c_int, ctypes.c_double] + [_c_fp] * 5 + [_c_fp]),
-    'gwtf_enc_train_backward': (ctypes.c_int, [ctypes.c_int] + [_c_fp] * 10 + [ctypes.c_int, ctypes.c_int, _c_fp]),
     'gwtf_enc_train_dw_partial_floats': (ctypes.c_size_t, [ctypes.c_int] * 3),
-    'gwtf_enc_train_dw': (ctypes.c_int, [ctypes.c_int] + [_c_fp] * 7 + [ctypes.c_int, ctypes.c_int, _c_fp]),
-    'gwtf_enc_train_dw3': (ctypes.c_int, [_c_fp] * 9 + [ctypes.c_int, ctypes.c_int, _c_fp]),
+    'gwtf_enc_train_phase': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    'gwtf_enc_train_forward': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_enc_train_backward': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_stat_compact': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_int, ctypes.c_int, _c_fp]),
     'gwtf_enc_train_mform_workspace_floats': (ctypes.c_size_t, [ctypes.c_int]),
     'gwtf_enc_train_mform': (ctypes.c_int, [_c_fp] * 5 + [ctypes.c_int, ctypes.c_int, _c_fp]),
@@ -130,6 +120,31 @@ class TrainCtx(ctypes.Structure):
                     'p', 'raw', 'packed_w', 'packed_b', 'film_raw', 'film_rec', 'moments', 'ystats', 'mom_c', 'ys_c', 'bn_batch', 'xbuf',
                     'logdet', 'ps', 'mus', 'logvars', 'g_out', 'g_ld', 'g_ps', 'g_lvs', 'g_bufs', 'g_xa', 'g_xb', 'dw1_ws', 'g_film', 'g_sd0',
                     'g_bias', 'g_stats', 'g_mom', 'g_film_raw', 'g_raw', 'stream')])
+
+
+ENC_PHASE_FWD_INIT, ENC_PHASE_FWD_LAYER, ENC_PHASE_BWD_TOP, ENC_PHASE_BWD_LAYER = range(4)
+
+
+class EncTrainCtx(ctypes.Structure):
+    """GwtfEncTrainCtx of include/gwtf.h (the encoder's train pipeline, both directions): same field order."""
+    _p, _p2, _p3, _p4 = ctypes.c_void_p, ctypes.c_void_p * 2, ctypes.c_void_p * 3, ctypes.c_void_p * 4
+    _fields_ = [('B', ctypes.c_int), ('N', ctypes.c_int), ('n_total', ctypes.c_double), ('momentum', ctypes.c_float * 4),
+                ('x', _p), ('W', _p4), ('gamma', _p4), ('beta', _p4), ('running_mean', _p4), ('running_var', _p4),
+                ('mom', _p), ('mom_c', _p), ('mom_fold', _p), ('sums', _p3), ('sums_c', _p3), ('sums_fold', _p3),
+                ('ymax', _p), ('kmax', _p), ('kmin', _p), ('aff', _p4), ('table0', _p), ('units_f', _p3), ('units_b', _p3), ('y', _p2),
+                ('pooled', _p), ('amax', _p), ('ystar', _p),
+                ('g_pooled', _p), ('gp', _p), ('gmax', _p), ('g_sums', _p3), ('g_sums_c', _p4), ('g_sums_r', _p4), ('bconst', _p4),
+                ('units_m', _p), ('mconst', _p), ('mform_ws', _p), ('extra', _p), ('slot_of', _p), ('tables', _p), ('a2rows', _p),
+                ('dA', _p2), ('partials', _p), ('gram', _p), ('S', _p), ('dW', _p4), ('stream', _p)]
+
+    def bind(self, bufs):
+        """self.<name> = the device address of bufs[name]: a tensor, or a list of tensors for a per-layer array field (None: NULL)."""
+        at = lambda b: None if b is None else b.data_ptr()
+        for name, b in bufs.items():
+            if isinstance(b, (list, tuple)):
+                getattr(self, name)[:] = [at(e) for e in b]
+            else:
+                setattr(self, name, at(b))
 
 
 class StackArgs(ctypes.Structure):

@@ -702,7 +702,7 @@ __global__ __launch_bounds__(kThreads, NB == 1 ? 4 : 1) void enc_train_bwd_kerne
 #pragma unroll
           for (int r = 0; r < 4; ++r) a[r] = fmaf(s4[r], y_prev[toff_p[nb] + (size_t)(c0 + r) * 32], t4[r]);
           split_into<true>(a, bhi[ks][nb], blo[ks][nb], half);
-          // the activations of the arg-max points, point-major: what the arg-max part of dW_3 contracts with (gwtf_enc_train_dw3).
+          // the activations of the arg-max points, point-major: what the arg-max part of dW_3 contracts with (dw3).
           // Here they are in registers; gathered from the (B, C, N) array afterwards every VALUE costs a 128-byte line (72 us).
           if (a2rows && slot[nb] >= 0) {
             f32x4 ar;
@@ -798,7 +798,7 @@ __global__ __launch_bounds__(kThreads, NB == 1 ? 4 : 1) void enc_train_bwd_kerne
           const float pre = fmaf(sp[r], yv, tp[r]);
           const bool on = valid[nb] && pre > 0.f;
           const float gm = on ? (TOP ? fmaf(acc[nb][r], down, bc[j] + ex_cur[nb][r]) : acc[nb][r] * down) : 0.f;
-          if (TOP) sx0 += on ? pre : 0.f;                  // sum_p a_{l-1}: the R term of dW_3 (gwtf_enc_train_dw3)
+          if (TOP) sx0 += on ? pre : 0.f;                  // sum_p a_{l-1}: the R term of dW_3 (dw3)
 #if GWTF_ENC_DBG == 1
           if (!BOTTOM && valid[nb] && gm == 123.456f) dA_prev[toff_p[nb] + (size_t)j * 32] = gm;
 #else
@@ -1184,148 +1184,124 @@ extern "C" size_t gwtf_enc_train_units_floats(int layer) {
   return (size_t)(kC[layer + 1] / 16) * (kC[layer] / 32) * 512;
 }
 
-// all three layers' images from one launch
-extern "C" int gwtf_enc_train_pack_all(const float* W1, const float* W2, const float* W3, float* uf1, float* ub1, float* uf2, float* ub2,
-                                       float* uf3, float* ub3, void* stream) {
-  if (!W1 || !W2 || !W3 || !uf1 || !ub1 || !uf2 || !ub2 || !uf3 || !ub3) return GWTF_E_BADARG;
-  PackJobs J;
-  const float* Ws[3] = {W1, W2, W3};
-  float* uf[3] = {uf1, uf2, uf3};
-  float* ub[3] = {ub1, ub2, ub3};
-  for (int l = 1; l <= 3; ++l) {
-    const int cin = kC[l], cout = kC[l + 1];
-    J.W[2 * (l - 1)] = Ws[l - 1]; J.units[2 * (l - 1)] = uf[l - 1]; J.rows[2 * (l - 1)] = cout; J.kdim[2 * (l - 1)] = cin; J.transposed[2 * (l - 1)] = 0;
-    J.W[2 * l - 1] = Ws[l - 1]; J.units[2 * l - 1] = ub[l - 1]; J.rows[2 * l - 1] = cin; J.kdim[2 * l - 1] = cout; J.transposed[2 * l - 1] = 1;
-  }
-  hipLaunchKernelGGL(enc_train_pack_all_kernel, dim3(64, 6), dim3(256), 0, (hipStream_t)stream, J);
-  return (int)hipGetLastError();
-}
-
-extern "C" int gwtf_enc_train_xmoments(const float* x, float* mom, int B, int N, void* stream) {
-  if (!x || !mom || B <= 0 || N <= 0) return GWTF_E_BADARG;
-  hipLaunchKernelGGL(enc_xmom_kernel, dim3((N + 1023) / 1024, B), dim3(256), 0, (hipStream_t)stream, x, mom, B, N);
-  return (int)hipGetLastError();
-}
-
-extern "C" int gwtf_enc_train_fold0(const float* mom12, double n_total, const float* W0, const float* gamma, const float* beta,
-                                    float* running_mean, float* running_var, float momentum, float* aff, float* table0,
-                                    void* stream) {
-  if (!mom12 || !W0 || !gamma || !beta || !aff || !table0 || n_total <= 0) return GWTF_E_BADARG;
-  hipLaunchKernelGGL(enc_fold0_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, mom12, n_total, W0, gamma, beta, running_mean,
-                     running_var, momentum, aff, table0, kC[1]);
-  return (int)hipGetLastError();
-}
-
-extern "C" int gwtf_enc_train_fold(const float* sums, int layer, double n_total, const float* gamma, const float* beta,
-                                   float* running_mean, float* running_var, float momentum, float* aff, const float* aff_prev,
-                                   void* stream) {
-  if (!sums || !gamma || !beta || !aff || !aff_prev || layer < 1 || layer > 3 || n_total <= 0) return GWTF_E_BADARG;
-  hipLaunchKernelGGL(enc_fold_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, sums, kC[layer + 1], n_total, gamma, beta,
-                     running_mean, running_var, momentum, aff, aff_prev);
-  return (int)hipGetLastError();
-}
-
-extern "C" int gwtf_enc_train_forward(int layer, const float* in, const float* in_tab, const float* units, float* y_out,
-                                      float* sums, float* ymax, unsigned long long* kmax, unsigned long long* kmin,
-                                      const float* gamma3, int B, int N, void* stream) {
-  if (!in || !in_tab || !units || !sums || !ymax || B <= 0 || N <= 0 || layer < 1 || layer > 3) return GWTF_E_BADARG;
-  if (layer < 3 ? !y_out : (!kmax || !kmin || !gamma3)) return GWTF_E_BADARG;
-  const dim3 block(kThreads);
-  auto grid = [&](int nb) { return dim3((N + 128 * nb - 1) / (128 * nb), B); };
-  hipStream_t st = (hipStream_t)stream;
-  if (layer == 1) hipLaunchKernelGGL((enc_train_fwd_kernel<64, 128, true, false, kNF1>), grid(kNF1), block, 0, st, in, in_tab, units, y_out, sums, ymax, kmax, kmin, B, N, gamma3);
-  else if (layer == 2) hipLaunchKernelGGL((enc_train_fwd_kernel<128, 256, false, false, kNF2>), grid(kNF2), block, 0, st, in, in_tab, units, y_out, sums, ymax, kmax, kmin, B, N, gamma3);
-  else hipLaunchKernelGGL((enc_train_fwd_kernel<256, 512, false, true, kNF3>), grid(kNF3), block, 0, st, in, in_tab, units, y_out, sums, ymax, kmax, kmin, B, N, gamma3);
-  return (int)hipGetLastError();
-}
-
-extern "C" int gwtf_enc_train_pool(const unsigned long long* kmax, const unsigned long long* kmin, const float* aff3, float* pooled,
-                                   int* amax, float* ystar, int B, int N, void* stream) {
-  if (!kmax || !kmin || !aff3 || !pooled || !amax || !ystar || B <= 0 || N <= 0) return GWTF_E_BADARG;
-  const int C = kC[4];
-  hipLaunchKernelGGL(enc_pool_finalize_kernel, dim3((B * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, kmax, kmin, aff3, pooled,
-                     amax, ystar, B, C, N);
-  return (int)hipGetLastError();
-}
-
-extern "C" int gwtf_enc_train_top_scatter(const float* coef, const float* scale, const int* amax, const float* W3, float* extra,
-                                          int* slot_of, int* tables, int B, int N, void* stream) {
-  if (!coef || !amax || !W3 || !extra || !slot_of || !tables || B <= 0 || N <= 0 || (size_t)N * sizeof(int) > 48 * 1024)
-    return GWTF_E_BADARG;
-  const int C = kC[4];
-  int* row_off = tables;                          // [B][C + 2]
-  int* row_list = tables + (size_t)B * (C + 2);   // [B][C]
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(enc_top_scatter_kernel, dim3(B), dim3(256), (size_t)N * sizeof(int), st, coef, scale, amax, slot_of, row_off,
-                     row_list,
-                     N, C);
-  hipLaunchKernelGGL(enc_top_rows_kernel, dim3((B * C + 3) / 4), dim3(256), 0, st, coef, scale, row_off, row_list, W3, extra, B, C,
-                     kC[3]);
-  return (int)hipGetLastError();
-}
-
-extern "C" int gwtf_enc_train_top(const float* g_pooled, const float* pooled, const float* ystar, const float* aff3, float* gp,
-                                  float* sums, float* gmax, int B, void* stream) {
-  if (!g_pooled || !pooled || !ystar || !aff3 || !gp || !sums || !gmax || B <= 0) return GWTF_E_BADARG;
-  const int C = kC[4];
-  hipLaunchKernelGGL(enc_top_kernel, dim3((C + 31) / 32), dim3(256), 0, (hipStream_t)stream, g_pooled, pooled, ystar, aff3, gp, sums,
-                     gmax, B, C);
-  return (int)hipGetLastError();
-}
-
-extern "C" int gwtf_enc_train_bwd_consts(const float* sums, int layer, double n_total, const float* gamma, const float* aff,
-                                         const float* gmax, const float* ymax, float* bconst, void* stream) {
-  if (!sums || !gamma || !aff || !bconst || layer < 0 || layer > 3 || n_total <= 0) return GWTF_E_BADARG;
-  hipLaunchKernelGGL(enc_bwd_consts_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, sums, kC[layer + 1], n_total, gamma, aff,
-                     gmax, ymax, bconst);
-  return (int)hipGetLastError();
-}
-
-extern "C" int gwtf_enc_train_backward(int layer, const float* y_l, const float* up_g, const float* bconst,
-                                       const float* units_bwd, const float* y_prev, const float* aff_prev, const float* w0,
-                                       float* dA_prev, float* sums, float* gmax_prev, int B, int N, void* stream) {
-  if (!y_l || !up_g || !bconst || !units_bwd || !y_prev || !aff_prev || !sums || B <= 0 || N <= 0 || layer < 1 || layer > 2)
-    return GWTF_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 block(kThreads);
-  if (layer == 2) {
-    if (!dA_prev || !gmax_prev) return GWTF_E_BADARG;
-    hipLaunchKernelGGL((enc_train_bwd_kernel<128, 256, kNB2, false, false>), dim3((N + 128 * kNB2 - 1) / (128 * kNB2), B), block, 0, st, y_l, up_g, nullptr, nullptr, bconst,
-                       units_bwd, y_prev, aff_prev, w0, dA_prev, sums, gmax_prev, B, N, 0, nullptr);
-  } else {
-    if (!w0) return GWTF_E_BADARG;
-    hipLaunchKernelGGL((enc_train_bwd_kernel<64, 128, kNB1, false, true>), dim3((N + 128 * kNB1 - 1) / (128 * kNB1), B), block, 0, st, y_l, up_g, nullptr, nullptr, bconst,
-                       units_bwd, y_prev, aff_prev, w0, dA_prev, sums, gmax_prev, B, N, 0, nullptr);
-  }
-  return (int)hipGetLastError();
-}
-
-// layer 3 in the M form (see enc_train_bwd_kernel): units_m = fragment images of M * 2^k, mconst = v [256] | {2^-k},
-// extra / slot_of from gwtf_enc_train_top_scatter; a2rows [B][512][256] (out): row slot_of[b][n] of shape b = a_2(b, :, n) for every
-// arg-max point n (the other rows are not written) -- what gwtf_enc_train_dw3 contracts the top gradients with
-extern "C" int gwtf_enc_train_backward_top(const float* y2, const float* aff2, const float* units_m, const float* mconst,
-                                           const float* extra, const int* slot_of, float* dA2, float* sums, float* gmax2,
-                                           float* a2rows, int B, int N, void* stream) {
-  if (!y2 || !aff2 || !units_m || !mconst || !extra || !slot_of || !dA2 || !sums || !gmax2 || !a2rows || B <= 0 || N <= 0)
-    return GWTF_E_BADARG;
-  hipLaunchKernelGGL((enc_train_bwd_kernel<256, 256, kNBT, true, false>), dim3((N + 128 * kNBT - 1) / (128 * kNBT), B), dim3(kThreads), 0,
-                     (hipStream_t)stream, nullptr, nullptr, extra, slot_of, mconst, units_m, y2, aff2, nullptr, dA2, sums, gmax2, B, N,
-                     kC[4], a2rows);
-  return (int)hipGetLastError();
-}
-
 extern "C" size_t gwtf_enc_train_dw_partial_floats(int layer, int B, int N) {
   if (layer < 1 || layer > 3 || B <= 0 || N <= 0) return 0;
-  // layer 3 goes through the Gram matrix of a_2 (C[3] x C[3]); see gwtf_enc_train_dw3
+  // layer 3 goes through the Gram matrix of a_2 (C[3] x C[3]); see dw3
   const int CA = layer == 3 ? kC[3] : kC[layer + 1];
   return (size_t)B * dw_slices_per_shape(layer) * CA * kC[layer];
 }
 
-extern "C" int gwtf_enc_train_dw(int layer, const float* y_l, const float* up_g, const float* bconst, const float* y_prev,
-                                 const float* tab_prev, float* partials, float* dW, int B, int N, void* stream) {
-  if (!y_l || !up_g || !bconst || !y_prev || !tab_prev || !partials || !dW || B <= 0 || N <= 0 || (N & 3) || layer < 1 || layer > 2)
-    return GWTF_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
+// ---- host side: the launches of one phase, operands from the record (GwtfEncTrainCtx, include/gwtf.h) ----
+namespace {
+
+template <class T, int n> bool all_set(T* const (&a)[n]) {        // every pointer of a per-layer array field
+  for (T* p : a)
+    if (!p) return false;
+  return true;
+}
+
+bool ctx_ok(const GwtfEncTrainCtx* t, bool backward) {
+  if (!t || t->B <= 0 || t->N <= 0 || (t->N & 3) || (size_t)t->N * sizeof(int) > 48 * 1024 || !(t->n_total > 0)) return false;
+  if (!t->x || !all_set(t->W) || !all_set(t->gamma) || !all_set(t->beta) || !t->mom || !t->mom_c || !t->mom_fold || !all_set(t->sums) ||
+      !all_set(t->sums_c) || !all_set(t->sums_fold) || !t->ymax || !t->kmax || !t->kmin || !all_set(t->aff) || !t->table0 ||
+      !all_set(t->units_f) || !all_set(t->units_b) || !all_set(t->y) || !t->pooled || !t->amax || !t->ystar)
+    return false;
+  if (backward && (!t->g_pooled || !t->gp || !t->gmax || !all_set(t->g_sums) || !all_set(t->g_sums_c) || !all_set(t->g_sums_r) ||
+                   !all_set(t->bconst) || !t->units_m || !t->mconst || !t->mform_ws || !t->extra || !t->slot_of || !t->tables ||
+                   !t->a2rows || !all_set(t->dA) || !t->partials || !t->gram || !t->S || !all_set(t->dW)))
+    return false;
+  return true;
+}
+
+// all three layers' images from one launch
+void pack_all(const GwtfEncTrainCtx* t, hipStream_t st) {
+  PackJobs J;
+  for (int l = 1; l <= 3; ++l) {
+    const int cin = kC[l], cout = kC[l + 1];
+    J.W[2 * (l - 1)] = t->W[l]; J.units[2 * (l - 1)] = t->units_f[l - 1]; J.rows[2 * (l - 1)] = cout; J.kdim[2 * (l - 1)] = cin; J.transposed[2 * (l - 1)] = 0;
+    J.W[2 * l - 1] = t->W[l]; J.units[2 * l - 1] = t->units_b[l - 1]; J.rows[2 * l - 1] = cin; J.kdim[2 * l - 1] = cout; J.transposed[2 * l - 1] = 1;
+  }
+  hipLaunchKernelGGL(enc_train_pack_all_kernel, dim3(64, 6), dim3(256), 0, st, J);
+}
+
+// the batch statistics of layer l -> aff[l] (layer 0: from the coordinate moments, and table0); running statistics updated
+void fold(const GwtfEncTrainCtx* t, int l, hipStream_t st) {
+  if (l == 0)
+    hipLaunchKernelGGL(enc_fold0_kernel, dim3(1), dim3(64), 0, st, t->mom_fold, t->n_total, t->W[0], t->gamma[0], t->beta[0], t->running_mean[0],
+                       t->running_var[0], t->momentum[0], t->aff[0], t->table0, kC[1]);
+  else
+    hipLaunchKernelGGL(enc_fold_kernel, dim3(1), dim3(512), 0, st, t->sums_fold[l - 1], kC[l + 1], t->n_total, t->gamma[l], t->beta[l],
+                       t->running_mean[l], t->running_var[l], t->momentum[l], t->aff[l], (const float*)t->aff[l - 1]);
+}
+
+// y_layer = W_layer . relu(s in + t): in = x and in_tab = table0 for layer 1, else y_{layer-1} and its aff.  Layer 3 stores no y, only the keys
+void forward_layer(const GwtfEncTrainCtx* t, int layer, hipStream_t st) {
+  const int B = t->B, N = t->N, i = layer - 1;
+  const bool top = layer == 3;
+  const float *in = layer == 1 ? t->x : t->y[i - 1], *in_tab = layer == 1 ? t->table0 : t->aff[i], *units = t->units_f[i];
+  const float* gamma3 = top ? t->gamma[3] : nullptr;
+  float *y_out = top ? nullptr : t->y[i], *sums = t->sums[i], *ymax = t->ymax + layer;
+  unsigned long long *kmax = top ? t->kmax : nullptr, *kmin = top ? t->kmin : nullptr;
+  const dim3 block(kThreads);
+  auto grid = [&](int nb) { return dim3((N + 128 * nb - 1) / (128 * nb), B); };
+  if (layer == 1) hipLaunchKernelGGL((enc_train_fwd_kernel<64, 128, true, false, kNF1>), grid(kNF1), block, 0, st, in, in_tab, units, y_out, sums, ymax, kmax, kmin, B, N, gamma3);
+  else if (layer == 2) hipLaunchKernelGGL((enc_train_fwd_kernel<128, 256, false, false, kNF2>), grid(kNF2), block, 0, st, in, in_tab, units, y_out, sums, ymax, kmax, kmin, B, N, gamma3);
+  else hipLaunchKernelGGL((enc_train_fwd_kernel<256, 512, false, true, kNF3>), grid(kNF3), block, 0, st, in, in_tab, units, y_out, sums, ymax, kmax, kmin, B, N, gamma3);
+}
+
+// layer = 0..3: the two BatchNorm-backward sums of y_layer -> bconst[layer]; the operand scale from gmax / ymax (layers 2, 1 only)
+void bwd_consts(const GwtfEncTrainCtx* t, int layer, hipStream_t st) {
+  const bool scaled = layer == 1 || layer == 2;
+  const float* gmax = scaled ? t->gmax + layer : nullptr;
+  const float* ymax = scaled ? t->ymax + layer : nullptr;
+  hipLaunchKernelGGL(enc_bwd_consts_kernel, dim3(1), dim3(512), 0, st, t->g_sums_r[layer], kC[layer + 1], t->n_total, t->gamma[layer],
+                     (const float*)t->aff[layer], gmax, ymax, t->bconst[layer]);
+}
+
+// coef = gp, scale = s_3 (row 0 of bconst[3]) -> slot_of, extra
+void top_scatter(const GwtfEncTrainCtx* t, hipStream_t st) {
+  const int B = t->B, N = t->N, C = kC[4];
+  const float *coef = t->gp, *scale = t->bconst[3];
+  int* row_off = t->tables;                          // [B][C + 2]
+  int* row_list = t->tables + (size_t)B * (C + 2);   // [B][C]
+  hipLaunchKernelGGL(enc_top_scatter_kernel, dim3(B), dim3(256), (size_t)N * sizeof(int), st, coef, scale, t->amax, t->slot_of, row_off,
+                     row_list,
+                     N, C);
+  hipLaunchKernelGGL(enc_top_rows_kernel, dim3((B * C + 3) / 4), dim3(256), 0, st, coef, scale, row_off, row_list, t->W[3], t->extra, B, C,
+                     kC[3]);
+}
+
+// layer = 2, 1: dA[layer - 2] = (W_layer^T dy_layer) masked by a_{layer-1} > 0 (layer 1 stores none), with the sums of the layer below.
+// y_prev / aff_prev: y_{layer-1} and its aff (layer 1: x, aff[0], and w0 = W[0])
+void backward_layer(const GwtfEncTrainCtx* t, int layer, hipStream_t st) {
+  const int B = t->B, N = t->N, i = layer - 1;
+  const float *y_l = t->y[i], *up_g = t->dA[i], *bconst = t->bconst[layer], *units_bwd = t->units_b[i];
+  const float *y_prev = layer == 1 ? t->x : t->y[i - 1], *aff_prev = t->aff[i], *w0 = layer == 1 ? t->W[0] : nullptr;
+  float *dA_prev = layer == 2 ? t->dA[0] : nullptr, *sums = t->g_sums[i], *gmax_prev = layer == 2 ? t->gmax + 1 : nullptr;
+  const dim3 block(kThreads);
+  if (layer == 2) {
+    hipLaunchKernelGGL((enc_train_bwd_kernel<128, 256, kNB2, false, false>), dim3((N + 128 * kNB2 - 1) / (128 * kNB2), B), block, 0, st, y_l, up_g, nullptr, nullptr, bconst,
+                       units_bwd, y_prev, aff_prev, w0, dA_prev, sums, gmax_prev, B, N, 0, nullptr);
+  } else {
+    hipLaunchKernelGGL((enc_train_bwd_kernel<64, 128, kNB1, false, true>), dim3((N + 128 * kNB1 - 1) / (128 * kNB1), B), block, 0, st, y_l, up_g, nullptr, nullptr, bconst,
+                       units_bwd, y_prev, aff_prev, w0, dA_prev, sums, gmax_prev, B, N, 0, nullptr);
+  }
+}
+
+// layer 3 in the M form (see enc_train_bwd_kernel): dA[1] = (M a_2 + v + extra) masked by a_2 > 0, the sums of layer 2, a2rows
+void backward_top(const GwtfEncTrainCtx* t, hipStream_t st) {
+  const int B = t->B, N = t->N;
+  hipLaunchKernelGGL((enc_train_bwd_kernel<256, 256, kNBT, true, false>), dim3((N + 128 * kNBT - 1) / (128 * kNBT), B), dim3(kThreads), 0,
+                     st, nullptr, nullptr, t->extra, t->slot_of, t->mconst, t->units_m, t->y[1], t->aff[2], nullptr, t->dA[1], t->g_sums[2],
+                     t->gmax + 2, B, N, kC[4], t->a2rows);
+}
+
+// layer = 2, 1: dW[layer] = sum over this rank's points of dy_layer a_{layer-1}^T; tab_prev = aff[layer - 1] (layer 1: table0, y_prev = x)
+void dw_layer(const GwtfEncTrainCtx* t, int layer, hipStream_t st) {
+  const int B = t->B, N = t->N, i = layer - 1;
+  const float *y_l = t->y[i], *up_g = t->dA[i], *bconst = t->bconst[layer];
+  const float *y_prev = layer == 1 ? t->x : t->y[i - 1], *tab_prev = layer == 1 ? t->table0 : t->aff[i];
+  float *partials = t->partials, *dW = t->dW[layer];
   const int CA = kC[layer + 1], CB = kC[layer], nsl = dw_slices_per_shape(layer), per = dw_per(layer, N);
   if (layer == 2)
     hipLaunchKernelGGL((enc_train_dw_kernel<4, 2, 0, false>), dim3(B * nsl), dim3(512), 0, st, y_l, up_g, bconst, y_prev, tab_prev, partials, B, N, nsl, per);
@@ -1333,21 +1309,81 @@ extern "C" int gwtf_enc_train_dw(int layer, const float* y_l, const float* up_g,
     hipLaunchKernelGGL((enc_train_dw_kernel<2, 1, 0, true>), dim3(B * nsl), dim3(128), 0, st, y_l, up_g, bconst, y_prev, tab_prev, partials, B, N, nsl, per);
   const int total = CA * CB;
   hipLaunchKernelGGL(enc_dw_reduce_kernel, dim3((total + 31) / 32), dim3(256), 0, st, partials, dW, B * nsl, total);
-  return (int)hipGetLastError();
 }
 
 // The top layer's weight gradient without a contraction over its 512 output channels: with dy_3 = s gm_3 + Q y_3 + R and
 // y_3 = W_3 a_2,   dW_3 = s (.) S + Q (.) (W_3 G_2) + R (x) sum_p a_2,   S[c][:] = sum_b gp[b][c] a_2(b, amax[b][c]) (gm_3 is
-// non-zero at the arg-max points only), G_2 = sum_p a_2 a_2^T.  This call leaves G_2 (256 x 256) and S (512 x 256); the caller
-// finishes with one small library GEMM (W_3 G_2) -- half the matrix work of the direct product and no pass over y_3.
-extern "C" int gwtf_enc_train_dw3(const float* gp, const int* amax, const int* slot_of, const float* a2rows, const float* y2,
-                                  const float* aff2, float* partials, float* gram, float* S, int B, int N, void* stream) {
-  if (!gp || !amax || !slot_of || !a2rows || !y2 || !aff2 || !partials || !gram || !S || B <= 0 || N <= 0 || (N & 3)) return GWTF_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
+// non-zero at the arg-max points only), G_2 = sum_p a_2 a_2^T.  This leaves G_2 (256 x 256) and S (512 x 256);
+// gwtf_enc_train_dw3_finish does the rest -- half the matrix work of the direct product and no pass over y_3.
+void dw3(const GwtfEncTrainCtx* t, hipStream_t st) {
+  const int B = t->B, N = t->N;
+  const float *y2 = t->y[1], *aff2 = t->aff[2];
+  float* partials = t->partials;
   const int C2 = kC[3], nsl = dw_slices_per_shape(3), per = dw_per(3, N);
   hipLaunchKernelGGL((enc_train_dw_kernel<4, 4, 2, false>), dim3(B * nsl), dim3(1024), 0, st, nullptr, nullptr, aff2, y2, aff2, partials,
                      B, N, nsl, per);
-  hipLaunchKernelGGL(enc_dw_reduce_kernel, dim3((C2 * C2 + 31) / 32), dim3(256), 0, st, partials, gram, B * nsl, C2 * C2);
-  hipLaunchKernelGGL(enc_top_gather_kernel, dim3(kC[4]), dim3(256), 0, st, gp, amax, slot_of, a2rows, S, B, N, kC[4], C2);
-  return (int)hipGetLastError();
+  hipLaunchKernelGGL(enc_dw_reduce_kernel, dim3((C2 * C2 + 31) / 32), dim3(256), 0, st, partials, t->gram, B * nsl, C2 * C2);
+  hipLaunchKernelGGL(enc_top_gather_kernel, dim3(kC[4]), dim3(256), 0, st, t->gp, t->amax, t->slot_of, t->a2rows, t->S, B, N, kC[4], C2);
+}
+
+}  // namespace
+
+extern "C" int gwtf_enc_train_phase(const GwtfEncTrainCtx* t, int phase, int layer) {
+  const bool bwd = phase == GWTF_ENC_PHASE_BWD_TOP || phase == GWTF_ENC_PHASE_BWD_LAYER;
+  if (phase < GWTF_ENC_PHASE_FWD_INIT || phase > GWTF_ENC_PHASE_BWD_LAYER || layer < 0 || layer > 3 || !ctx_ok(t, bwd)) return GWTF_E_BADARG;
+  const int B = t->B, N = t->N, C = kC[4];
+  hipStream_t st = (hipStream_t)t->stream;
+  int rc = 0;
+  switch (phase) {
+    case GWTF_ENC_PHASE_FWD_INIT:
+      hipLaunchKernelGGL(enc_xmom_kernel, dim3((N + 1023) / 1024, B), dim3(256), 0, st, t->x, t->mom, B, N);
+      rc = gwtf_stat_compact(t->mom, t->mom_c, kR, 12, st);
+      break;
+    case GWTF_ENC_PHASE_FWD_LAYER:
+      fold(t, layer, st);
+      if (layer == 0) pack_all(t, st);
+      if (layer < 3) {
+        forward_layer(t, layer + 1, st);
+        rc = gwtf_stat_compact(t->sums[layer], t->sums_c[layer], kR, 2 * kC[layer + 2], st);
+      } else {
+        hipLaunchKernelGGL(enc_pool_finalize_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, t->kmax, t->kmin, t->aff[3], t->pooled,
+                           t->amax, t->ystar, B, C, N);
+      }
+      break;
+    case GWTF_ENC_PHASE_BWD_TOP:
+      hipLaunchKernelGGL(enc_top_kernel, dim3((C + 31) / 32), dim3(256), 0, st, t->g_pooled, t->pooled, t->ystar, t->aff[3], t->gp, t->g_sums_c[3],
+                         t->gmax + 3, B, C);
+      break;
+    default:   // GWTF_ENC_PHASE_BWD_LAYER
+      bwd_consts(t, layer, st);
+      if (layer == 3) {
+        rc = gwtf_enc_train_mform(t->W[3], t->bconst[3], t->mform_ws, t->units_m, t->mconst, kC[3], kC[4], st);
+        if (rc) break;
+        top_scatter(t, st);
+        backward_top(t, st);
+        rc = gwtf_stat_compact(t->g_sums[2], t->g_sums_c[2], kR, 3 * kC[3], st);
+        if (rc) break;
+        dw3(t, st);
+        rc = gwtf_enc_train_dw3_finish(t->bconst[3], t->S, t->W[3], t->gram, t->g_sums_c[2] + 2 * kC[3], t->dW[3], kC[3], kC[4], st);
+      } else if (layer > 0) {
+        backward_layer(t, layer, st);
+        dw_layer(t, layer, st);
+        rc = gwtf_stat_compact(t->g_sums[layer - 1], t->g_sums_c[layer - 1], kR, (layer == 1 ? 5 : 2) * kC[layer], st);
+      } else {
+        rc = gwtf_enc_train_dw0_finish(t->bconst[0], t->g_sums_c[0], t->W[0], t->mom_c, t->dW[0], kC[1], st);
+      }
+  }
+  return rc ? rc : (int)hipGetLastError();
+}
+
+extern "C" int gwtf_enc_train_forward(const GwtfEncTrainCtx* t) {
+  int rc = gwtf_enc_train_phase(t, GWTF_ENC_PHASE_FWD_INIT, 0);
+  for (int l = 0; l < 4 && !rc; ++l) rc = gwtf_enc_train_phase(t, GWTF_ENC_PHASE_FWD_LAYER, l);
+  return rc;
+}
+
+extern "C" int gwtf_enc_train_backward(const GwtfEncTrainCtx* t) {
+  int rc = gwtf_enc_train_phase(t, GWTF_ENC_PHASE_BWD_TOP, 0);
+  for (int l = 3; l >= 0 && !rc; --l) rc = gwtf_enc_train_phase(t, GWTF_ENC_PHASE_BWD_LAYER, l);
+  return rc;
 }

@@ -13,6 +13,7 @@ without kernels, an input that itself requires a gradient.  CPU tensors raise: t
 (FeatureEncoder, WeightsEncoder) run one HIP launch per layer, forward and backward (csrc/gwtf_heads.hip, ``_HeadLayerFn``), for any
 number of rows (the gathered rows of a large data-parallel batch are walked 64 / 128 at a time inside the kernels).
 """
+import ctypes
 import os
 from collections import OrderedDict
 
@@ -31,181 +32,111 @@ def _bn_sync(bn):
     return isinstance(bn, nn.SyncBatchNorm) and sharded()
 
 
+def _over_ranks(src, dst):
+    """dst = src summed over the ranks: the statistic record a synchronised run exchanges between two phases of the pipeline."""
+    import torch.distributed as dist
+    from .dist import run
+    dst.copy_(src)
+    run(dist.all_reduce, dst, op=dist.ReduceOp.SUM)
+
+
 class _EncoderTrainFn(torch.autograd.Function):
     """pooled (B,512) = max over points of the train-mode encoder, csrc/gwtf_encoder_train.hip.  params = (W, bn.weight,
     bn.bias) of the four layers; ``enc`` supplies the BatchNorm buffers (running statistics are updated in place, as
-    F.batch_norm does)."""
+    F.batch_norm does).  Both directions fill one _lib.EncTrainCtx (include/gwtf.h GwtfEncTrainCtx: what every buffer is) and make one
+    call -- or, synchronised, walk the phases and sum the named statistic record over the ranks between them."""
 
     @staticmethod
     def forward(ctx, x, enc, sync, *params):
-        import torch.distributed as dist
-        from .dist import run as _run
+        from .autograd import _zero_arena
+        from .dist import row_layout
         L = _lib.lib()
         x = x.contiguous()
         B, _, N = x.shape
-        dev, st = x.device, _stream(x)
-        R = _lib.STAT_REPLICAS
-        C = enc._widths
-        bns = [m for m in enc.features.children() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
-        Ws = [w.detach().reshape(C[l + 1], C[l]).contiguous() for l, w in enumerate(params[0::3])]
-        gam = [g.detach().contiguous() for g in params[1::3]]
-        bet = [b.detach().contiguous() for b in params[2::3]]
+        dev, R, C = x.device, _lib.STAT_REPLICAS, enc._widths
+        bns = enc._bns()
+        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, device=dev, dtype=dtype)
+        # every zero-initialised accumulator of the forward pass from ONE fill: {coordinate moments, layer sums, maxima, keys}
+        zero = _zero_arena(dict(mom=(R, 12), sums1=(R, 2, C[2]), sums2=(R, 2, C[3]), sums3=(R, 2, C[4]), ymax=(4,),
+                                keys=(2, B, 2 * C[4])), dev)                 # keys: 64-bit arg-max / arg-min keys of y_3 (never stored)
+        units = [L.gwtf_enc_train_units_floats(l) for l in (1, 2, 3)]
+        buf = dict(
+            x=x, W=[w.detach().reshape(C[l + 1], C[l]).contiguous() for l, w in enumerate(params[0::3])],
+            gamma=[g.detach().contiguous() for g in params[1::3]], beta=[b.detach().contiguous() for b in params[2::3]],
+            running_mean=[bn.running_mean if bn.track_running_stats else None for bn in bns],
+            running_var=[bn.running_var if bn.track_running_stats else None for bn in bns],
+            mom=zero['mom'], mom_c=new(12), sums=[zero[f'sums{l}'] for l in (1, 2, 3)], sums_c=[new(2, C[l + 1]) for l in (1, 2, 3)],
+            ymax=zero['ymax'], kmax=zero['keys'][0], kmin=zero['keys'][1], aff=[new(4 * C[l + 1]) for l in range(4)], table0=new(4 * C[1]),
+            units_f=[new(n) for n in units], units_b=[new(n) for n in units],
+            # y_1, y_2 (and the backward's dA arrays) in tiles of 32 points x all channels: include/gwtf.h gwtf_enc_train_act_floats
+            y=[new(L.gwtf_enc_train_act_floats(B, C[l + 1], N)) for l in (1, 2)],
+            pooled=new(B, C[4]), amax=new(B, C[4], dtype=torch.int32), ystar=new(B, C[4]))
+        for given in (x, *buf['W'], *buf['gamma'], *buf['beta'], *buf['running_mean'], *buf['running_var']):
+            _ptr(given, 'encoder operand')                   # device / dtype / layout checks of what the caller handed in
+        # what the folds read: this rank's compact records, or their copies summed over the ranks
+        buf['mom_fold'] = new(12) if sync else buf['mom_c']
+        buf['sums_fold'] = [torch.empty_like(t) for t in buf['sums_c']] if sync else buf['sums_c']
         # points the statistics cover: every rank's shapes (the per-rank batch may differ by one, train_ae.py:77-78; the counts
         # are exchanged once and cached, dist.row_layout)
-        from .dist import row_layout
-        n_total = float((row_layout(B, dev).total if sync else B) * N)
-        f32 = dict(device=dev, dtype=torch.float32)
-        P = lambda t: 0 if t is None else _ptr(t, 'encoder buffer')
-        rm = [bn.running_mean if bn.track_running_stats else None for bn in bns]
-        rv = [bn.running_var if bn.track_running_stats else None for bn in bns]
-
-        def over_ranks(t):
-            if sync:
-                t = t.clone()
-                _run(dist.all_reduce, t, op=dist.ReduceOp.SUM)
-            return t
-
-        def compact(slab):
-            """sum of the R replicas of a statistic slab (R, ...) in one small launch (a torch sum over 64 rows takes 7 us)"""
-            out = torch.empty(slab.shape[1:], **f32)
-            check(L.gwtf_stat_compact(P(slab), P(out), slab.shape[0], out.numel(), st))
-            return out
-
+        t = _lib.EncTrainCtx(B=B, N=N, n_total=float((row_layout(B, dev).total if sync else B) * N), stream=_stream(x))
+        t.momentum[:] = [float(bn.momentum) for bn in bns]
+        t.bind(buf)
         with torch.cuda.device(dev):
-            # every zero-initialised accumulator of the forward pass from ONE fill: {coordinate moments, layer sums, maxima, keys}
-            sizes = [R * 12] + [R * 2 * C[l + 1] for l in (1, 2, 3)] + [4, 2 * (2 * B * C[4])]
-            zero = torch.zeros(sum(sizes), **f32).split(sizes)
-            mom, sums_l, ymax = zero[0].view(R, 12), {l: zero[l].view(R, 2, C[l + 1]) for l in (1, 2, 3)}, zero[4]
-            keys = zero[5].view(torch.int64).view(2, B, C[4])                    # arg-max / arg-min keys of y_3 (never stored)
-            check(L.gwtf_enc_train_xmoments(P(x), P(mom), B, N, st))
-            mom_local = compact(mom)
-            aff = [torch.empty(4 * C[l + 1], **f32) for l in range(4)]
-            table0 = torch.empty(4 * C[1], **f32)
-            check(L.gwtf_enc_train_fold0(P(over_ranks(mom_local)), n_total, P(Ws[0]), P(gam[0]), P(bet[0]), P(rm[0]), P(rv[0]),
-                                         float(bns[0].momentum), P(aff[0]), P(table0), st))
-            units_f, units_b = [None], [None]
-            for l in (1, 2, 3):
-                n_units = L.gwtf_enc_train_units_floats(l)
-                units_f.append(torch.empty(n_units, **f32))
-                units_b.append(torch.empty(n_units, **f32))
-            check(L.gwtf_enc_train_pack_all(P(Ws[1]), P(Ws[2]), P(Ws[3]), P(units_f[1]), P(units_b[1]), P(units_f[2]), P(units_b[2]),
-                                            P(units_f[3]), P(units_b[3]), st))       # one launch for the six fragment images
-            ys = [None]
-            for l in (1, 2, 3):
-                # y_1, y_2 (and the backward's dA arrays) in tiles of 32 points x all channels: include/gwtf.h gwtf_enc_train_act_floats
-                y = torch.empty(L.gwtf_enc_train_act_floats(B, C[l + 1], N), **f32) if l < 3 else None
-                sums = sums_l[l]
-                check(L.gwtf_enc_train_forward(l, P(x if l == 1 else ys[l - 1]), P(table0 if l == 1 else aff[l - 1]),
-                                               P(units_f[l]), P(y), P(sums), P(ymax[l:l + 1]),
-                                               keys[0].data_ptr() if l == 3 else 0, keys[1].data_ptr() if l == 3 else 0,
-                                               P(gam[3]) if l == 3 else 0, B, N, st))
-                check(L.gwtf_enc_train_fold(P(over_ranks(compact(sums))), l, n_total, P(gam[l]), P(bet[l]), P(rm[l]), P(rv[l]),
-                                            float(bns[l].momentum), P(aff[l]), P(aff[l - 1]), st))
-                ys.append(y)
-            pooled = torch.empty(B, C[4], **f32)
-            amax = torch.empty(B, C[4], device=dev, dtype=torch.int32)
-            ystar = torch.empty(B, C[4], **f32)
-            check(L.gwtf_enc_train_pool(keys[0].data_ptr(), keys[1].data_ptr(), P(aff[3]), P(pooled), amax.data_ptr(), P(ystar), B, N, st))
+            if not sync:
+                check(L.gwtf_enc_train_forward(ctypes.addressof(t)))
+            else:
+                check(L.gwtf_enc_train_phase(ctypes.addressof(t), _lib.ENC_PHASE_FWD_INIT, 0))
+                _over_ranks(buf['mom_c'], buf['mom_fold'])
+                for l in range(4):
+                    check(L.gwtf_enc_train_phase(ctypes.addressof(t), _lib.ENC_PHASE_FWD_LAYER, l))
+                    if l < 3:
+                        _over_ranks(buf['sums_c'][l], buf['sums_fold'][l])
             counters = [bn.num_batches_tracked for bn in bns if bn.track_running_stats and bn.num_batches_tracked is not None]
             if counters:
                 torch._foreach_add_(counters, 1)                                 # (one launch for the four counters)
-        ctx.save_for_backward(x, pooled, *params)
-        ctx.buf = dict(ys=ys, aff=aff, table0=table0, units_b=units_b, ymax=ymax, amax=amax, ystar=ystar,
-                       mom_local=mom_local, Ws=Ws, gam=gam)
-        ctx.meta = (B, N, n_total, sync, tuple(C))
+        # the record and the tensors behind its pointers stay on ctx; the outputs go through save_for_backward (pooled -> grad_fn ->
+        # ctx -> pooled would be a cycle that only the garbage collector frees, and every buffer of the step with it)
+        pooled, amax = buf.pop('pooled'), buf.pop('amax')
+        ctx.save_for_backward(x, pooled, amax, *params)
+        ctx.rec, ctx.buf, ctx.meta = t, buf, (sync, tuple(C))
         ctx.mark_non_differentiable(amax)
         return pooled, amax
 
     @staticmethod
     def backward(ctx, g_pooled, _g_amax):
-        import torch.distributed as dist
-        from .dist import run as _run
+        from .autograd import _zero_arena
         L = _lib.lib()
-        x, pooled, *params = ctx.saved_tensors
-        b = ctx.buf
-        B, N, n_total, sync, C = ctx.meta
-        ys, aff, Ws, gam = b['ys'], b['aff'], b['Ws'], b['gam']
-        dev, st = x.device, _stream(x)
-        R = _lib.STAT_REPLICAS
-        f32 = dict(device=dev, dtype=torch.float32)
-        P = lambda t: 0 if t is None else _ptr(t, 'encoder buffer')
-
-        def over_ranks(t):
-            if sync:
-                t = t.clone()
-                _run(dist.all_reduce, t, op=dist.ReduceOp.SUM)
-            return t
-
-        def compact(slab):
-            out = torch.empty(slab.shape[1:], **f32)
-            check(L.gwtf_stat_compact(P(slab), P(out), slab.shape[0], out.numel(), st))
-            return out
-
-        grads = [None] * 12
+        x, _pooled, _amax, *params = ctx.saved_tensors
+        t, (sync, C) = ctx.rec, ctx.meta
+        B, N, dev, R = t.B, t.N, x.device, _lib.STAT_REPLICAS
+        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, device=dev, dtype=dtype)
+        # every zero-initialised accumulator of the backward pass from ONE fill
+        zero = _zero_arena(dict(gmax=(4,), g0=(R, 5, C[1]), g1=(R, 2, C[2]), g2=(R, 3, C[3])), dev)
+        buf = dict(
+            g_pooled=g_pooled.contiguous().float(), gp=new(B, C[4]), gmax=zero['gmax'], g_sums=[zero['g0'], zero['g1'], zero['g2']],
+            g_sums_c=[new(5, C[1]), new(2, C[2]), new(3, C[3]), new(2, C[4])], bconst=[new(3 * C[l + 1] + 4) for l in range(4)],
+            units_m=new(L.gwtf_enc_train_units_floats(3) // 2), mconst=new(C[3] + 4),
+            mform_ws=new(L.gwtf_enc_train_mform_workspace_floats(C[3])), extra=new(B, C[4], C[3]),
+            slot_of=new(B, N, dtype=torch.int32), tables=new(B * (2 * C[4] + 2), dtype=torch.int32), a2rows=new(B, C[4], C[3]),
+            dA=[new(L.gwtf_enc_train_act_floats(B, C[l + 1], N)) for l in (1, 2)],
+            partials=new(max(L.gwtf_enc_train_dw_partial_floats(l, B, N) for l in (1, 2, 3))), gram=new(C[3], C[3]), S=new(C[4], C[3]),
+            dW=[new(C[l + 1], C[l]) for l in range(4)])
+        # what the consts kernels read: the first two rows of this rank's compact sums, or their copies summed over the ranks
+        buf['g_sums_r'] = [new(2, C[l + 1]) for l in range(4)] if sync else buf['g_sums_c']
+        _ptr(buf['g_pooled'], 'g_pooled')
+        t.bind(buf)
+        t.stream = _stream(x)
         with torch.cuda.device(dev):
-            g_pooled = g_pooled.contiguous().float()
-            gp = torch.empty(B, C[4], **f32)
-            red = torch.empty(2, C[4], **f32)
-            # every zero-initialised accumulator of the backward pass from ONE fill
-            sizes = [4, R * 3 * C[3], R * 2 * C[2], R * 5 * C[1]]
-            zero = torch.zeros(sum(sizes), **f32).split(sizes)
-            gmax, sums_l = zero[0], {3: zero[1].view(R, 3, C[3]), 2: zero[2].view(R, 2, C[2]), 1: zero[3].view(R, 5, C[1])}
-            check(L.gwtf_enc_train_top(P(g_pooled), P(pooled), P(b['ystar']), P(aff[3]), P(gp), P(red), P(gmax[3:4]), B, st))
-            partials = torch.empty(max(L.gwtf_enc_train_dw_partial_floats(l, B, N) for l in (1, 2, 3)), **f32)
-            # ---- layer 3 in the M form (csrc/gwtf_encoder_train.hip): dy_3 = s gm_3 + Q y_3 + R with y_3 = W_3 a_2 ----
-            grads[10], grads[11] = red[1], red[0]            # (views of `red`: nothing writes it again; a clone each was 8 launches per step)
-            bconst = torch.empty(3 * C[4] + 4, **f32)
-            check(L.gwtf_enc_train_bwd_consts(P(over_ranks(red[:2].contiguous())), 3, n_total, P(gam[3]), P(aff[3]), 0, 0, P(bconst), st))
-            W3 = Ws[3]
-            # M = W3^T diag(q3) W3 (256 x 256), its power-of-two operand scale, the fragment images of M 2^k and
-            # mconst = {W3^T r3, 2^-k}: two launches (csrc/gwtf_encoder_glue.hip; as torch operators: a batched library GEMM, a
-            # GEMV and 14 element-wise / reduction launches, ~85 us)
-            units_m = torch.empty(L.gwtf_enc_train_units_floats(3) // 2, **f32)
-            mconst = torch.empty(C[3] + 4, **f32)
-            mws = torch.empty(L.gwtf_enc_train_mform_workspace_floats(C[3]), **f32)
-            check(L.gwtf_enc_train_mform(P(W3), P(bconst), P(mws), P(units_m), P(mconst), C[3], C[4], st))
-            extra = torch.empty(B, C[4], C[3], **f32)
-            slot_of = torch.empty(B, N, device=dev, dtype=torch.int32)
-            tables = torch.empty(B * (2 * C[4] + 2), device=dev, dtype=torch.int32)
-            check(L.gwtf_enc_train_top_scatter(P(gp), bconst.data_ptr(), b['amax'].data_ptr(), P(W3), P(extra),      # coef = gp s_3
-                                               slot_of.data_ptr(), tables.data_ptr(), B, N, st))
-            up = torch.empty(L.gwtf_enc_train_act_floats(B, C[3], N), **f32)       # masked dL/da_2 (tiled like y_2)
-            sums = sums_l[3]
-            a2rows = torch.empty(B, C[4], C[3], **f32)                             # a_2 at the arg-max points, point-major
-            check(L.gwtf_enc_train_backward_top(P(ys[2]), P(aff[2]), P(units_m), P(mconst), P(extra), slot_of.data_ptr(), P(up),
-                                                P(sums), P(gmax[2:3]), P(a2rows), B, N, st))
-            red = compact(sums)
-            # dW_3 = s (.) S + Q (.) (W_3 G_2) + R (x) sum_p a_2  (gwtf_enc_train_dw3, gwtf_enc_train_dw3_finish)
-            gram, S = torch.empty(C[3], C[3], **f32), torch.empty(C[4], C[3], **f32)
-            check(L.gwtf_enc_train_dw3(P(gp), b['amax'].data_ptr(), slot_of.data_ptr(), P(a2rows), P(ys[2]), P(aff[2]), P(partials), P(gram),
-                                       P(S), B, N, st))
-            dW3 = torch.empty(C[4], C[3], **f32)
-            check(L.gwtf_enc_train_dw3_finish(P(bconst), P(S), P(W3), P(gram), red[2].data_ptr(), P(dW3), C[3], C[4], st))
-            grads[9] = dW3.view_as(params[9])
-            for l in (2, 1):
-                grads[3 * l + 1], grads[3 * l + 2] = red[1], red[0]                          # bn.weight, bn.bias of layer l
-                bconst = torch.empty(3 * C[l + 1] + 4, **f32)
-                check(L.gwtf_enc_train_bwd_consts(P(over_ranks(red[:2].contiguous())), l, n_total, P(gam[l]), P(aff[l]),
-                                                  P(gmax[l:l + 1]), P(b['ymax'][l:l + 1]), P(bconst), st))
-                dA = torch.empty(L.gwtf_enc_train_act_floats(B, C[l], N), **f32) if l > 1 else None
-                sums = sums_l[l]
-                check(L.gwtf_enc_train_backward(l, P(ys[l]), P(up), P(bconst), P(b['units_b'][l]), P(x if l == 1 else ys[l - 1]),
-                                                P(aff[l - 1]), P(Ws[0] if l == 1 else None), P(dA), P(sums),
-                                                P(gmax[l - 1:l]) if l > 1 else 0, B, N, st))
-                dW = torch.empty(C[l + 1], C[l], **f32)
-                check(L.gwtf_enc_train_dw(l, P(ys[l]), P(up), P(bconst), P(x if l == 1 else ys[l - 1]),
-                                          P(b['table0'] if l == 1 else aff[l - 1]), P(partials), P(dW), B, N, st))
-                grads[3 * l] = dW.view_as(params[3 * l])
-                red = compact(sums)
-                up = dA
-            # layer 0 (3 -> 64): every sum its gradient needs is already there
-            grads[1], grads[2] = red[1], red[0]
-            bconst = torch.empty(3 * C[1] + 4, **f32)
-            check(L.gwtf_enc_train_bwd_consts(P(over_ranks(red[:2].contiguous())), 0, n_total, P(gam[0]), P(aff[0]), 0, 0,
-                                              P(bconst), st))
-            dW0 = torch.empty(C[1], 3, **f32)
-            check(L.gwtf_enc_train_dw0_finish(P(bconst), P(red), P(Ws[0]), P(b['mom_local']), P(dW0), C[1], st))
-            grads[0] = dW0.view_as(params[0])
+            if not sync:
+                check(L.gwtf_enc_train_backward(ctypes.addressof(t)))
+            else:
+                check(L.gwtf_enc_train_phase(ctypes.addressof(t), _lib.ENC_PHASE_BWD_TOP, 0))
+                for l in (3, 2, 1, 0):
+                    _over_ranks(buf['g_sums_c'][l][:2], buf['g_sums_r'][l])
+                    check(L.gwtf_enc_train_phase(ctypes.addressof(t), _lib.ENC_PHASE_BWD_LAYER, l))
+        grads = []
+        for l in range(4):               # W, bn.weight, bn.bias of layer l (views of this rank's compact sums: nothing writes them again)
+            grads += [buf['dW'][l].view_as(params[3 * l]), buf['g_sums_c'][l][1], buf['g_sums_c'][l][0]]
         return (None, None, None, *grads)
 
 
@@ -252,8 +183,10 @@ class PointNetCloudEncoder(nn.Module):
         self._packed = None
         return super().load_state_dict(*a, **k)
 
+    def _bns(self):
+        return [m for m in self.features.children() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+
     def _widths_c(self):
-        import ctypes
         return (ctypes.c_int * len(self._widths))(*self._widths), len(self._widths)
 
     def packed(self):
@@ -317,7 +250,7 @@ class PointNetCloudEncoder(nn.Module):
             return False
         if torch.is_grad_enabled() and x.requires_grad:
             return False
-        bns = [m for m in self.features.children() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+        bns = self._bns()
         if any(bn.momentum is None or not bn.affine or not bn.training for bn in bns):     # a frozen (eval) BatchNorm: library path
             return False
         if len({_bn_sync(bn) for bn in bns}) > 1:                                            # mixed plain / synchronised modules
@@ -339,8 +272,7 @@ class PointNetCloudEncoder(nn.Module):
         materialises the (B,C_last,N) tensor, train mode runs csrc/gwtf_encoder_train.hip (forward and backward)."""
         _ptr(input if input.is_contiguous() else input.contiguous(), 'input')
         if self._train_pipeline_ok(input):
-            bns = [m for m in self.features.children() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
-            pooled, amax = _EncoderTrainFn.apply(input, self, _bn_sync(bns[0]), *self._train_params())
+            pooled, amax = _EncoderTrainFn.apply(input, self, _bn_sync(self._bns()[0]), *self._train_params())
             return (pooled, amax) if return_indices else pooled
         if self._needs_graph(input):
             pooled, amax = torch.max(self.features(input), dim=2)

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define GWTF_ABI_VERSION 10
+#define GWTF_ABI_VERSION 11
 #define GWTF_E_BADARG 10001   /* shape / mode / width outside what the kernels support */
 #define GWTF_E_UNSUPPORTED 10002   /* a layer-width list no kernel instantiation was built for */
 #define GWTF_MODE_DIRECT 0    /* sampling direction  base -> data (reference models.py:202) */
@@ -367,7 +367,7 @@ int gwtf_encoder_forward(const float* x, const float* packed, float* features, f
  * folded into layer 1's prologue).  x is the reference's (B, 3, N) fp32 tensor; the stored activations y_1, y_2 and gradients dA_2, dA_1 are
  * fp32 in tiles of 32 points, [B][ceil(N/32)][C][32] (gwtf_enc_train_act_floats): written and read by these entry points only.
  *   aff     [4][C]  = s, t, mean, rstd of a layer's BatchNorm (a = relu(s y + t));  table0 [64][4] = (s W_0 row, t)
- *   sums    replicated accumulators, zero on entry: the caller sums the 64 replicas (and the ranks) before the fold
+ *   sums    replicated accumulators, zero on entry: a phase sums the 64 replicas, the caller the ranks, before the fold
  *   bconst  [3][C] + 4: dy = s gm + Q y + R per channel, then {up, down} = the power-of-two scale of the f16-split operand
  * gwtf_enc_train_supported(widths, n) -> 1 when this width list has kernels. */
 int gwtf_enc_train_supported(const int* widths, int n_widths);
@@ -376,80 +376,95 @@ size_t gwtf_enc_train_units_floats(int layer);
  * tiles of 32 points, [B][ceil(N / 32)][channels][32] + one spare tile (a wave / a k-step takes 32 points x all channels: one contiguous block), NOT in the
  * reference's (B, C, N); only x (B, 3, N) and the pooled (B, 512) outputs keep the reference's layouts. */
 size_t gwtf_enc_train_act_floats(int B, int channels, int N);
-/* W_l [C[l+1]][C[l]] -> MFMA fragment images of W_l (forward, uf_l) and W_l^T (backward, ub_l) for layers 1, 2, 3 from ONE launch,
- * gwtf_enc_train_units_floats(l) floats each */
-int gwtf_enc_train_pack_all(const float* W1, const float* W2, const float* W3, float* uf1, float* ub1, float* uf2, float* ub2,
-                            float* uf3, float* ub3, void* stream);
-/* mom [64][12] += {sum x (3), sum x x^T (xx xy xz yy yz zz), -} over this rank's points */
-int gwtf_enc_train_xmoments(const float* x, float* mom, int B, int N, void* stream);
-/* layer 0: batch statistics of y_0 = W_0 x from the summed moments mom12; updates the running statistics (NULL: skip) */
-int gwtf_enc_train_fold0(const float* mom12, double n_total, const float* W0, const float* gamma, const float* beta,
-                         float* running_mean, float* running_var, float momentum, float* aff, float* table0, void* stream);
-/* sums [2][C[layer+1]] = sum y, sum y^2 -> aff of that layer's BatchNorm; running statistics updated (momentum, unbiased var).
- * aff_prev = the aff of the layer below: non-finite statistics there or here poison this whole aff with NaN (NaN propagation) */
-int gwtf_enc_train_fold(const float* sums, int layer, double n_total, const float* gamma, const float* beta,
-                        float* running_mean, float* running_var, float momentum, float* aff, const float* aff_prev,
-                        void* stream);
-/* y_out (C[layer+1] channels, tiled) = W_layer . relu(s in + t); in = x and in_tab = table0 for layer 1, else y_{layer-1} and its aff.
- * sums [64][2][C[layer+1]] += {sum y, sum y^2}; ymax[0] = max |y| (bit pattern max, zero on entry).
- * layer 3 stores no y: kmax / kmin [B][512] (zero on entry) receive the 64-bit arg-max (channels with BatchNorm weight gamma3 >= 0)
- * or arg-min (gamma3 < 0) key of y_3 per (shape, channel) -- all the max-pool needs, because BatchNorm + ReLU is monotone in y per
- * channel, rising or falling with the sign of gamma3 (the other array's entry stays zero; y_out may be NULL; kmax / kmin / gamma3
- * NULL for layers 1, 2) */
-int gwtf_enc_train_forward(int layer, const float* in, const float* in_tab, const float* units, float* y_out, float* sums,
-                           float* ymax, unsigned long long* kmax, unsigned long long* kmin, const float* gamma3, int B, int N,
-                           void* stream);
-/* pooled (B,512) = max_n relu(s y3 + t) from the keys (max or min by the sign of s), amax = its first arg-max, ystar = y3 there;
- * NaN where a statistic or the extreme is not finite */
-int gwtf_enc_train_pool(const unsigned long long* kmax, const unsigned long long* kmin, const float* aff3, float* pooled, int* amax,
-                        float* ystar, int B, int N, void* stream);
-/* gp = g_pooled where pooled > 0; sums [2][512] = {sum gp, sum gp yhat*}; gmax[0] = max |gp| (zero on entry) */
-int gwtf_enc_train_top(const float* g_pooled, const float* pooled, const float* ystar, const float* aff3, float* gp, float* sums,
-                       float* gmax, int B, void* stream);
-/* layer = 0..3 (BatchNorm of y_layer): sums [2][C[layer+1]] = {sum gm, sum gm yhat} over all points and ranks -> bconst;
- * gmax / ymax (may be NULL): the maxima the operand scale is derived from */
-int gwtf_enc_train_bwd_consts(const float* sums, int layer, double n_total, const float* gamma, const float* aff,
-                              const float* gmax, const float* ymax, float* bconst, void* stream);
-/* Top layer: with dy_3 = s gm_3 + Q y_3 + R and y_3 = W_3 a_2,  dL/da_2(p) = M a_2(p) + v + (rows of the arg-max points),
- * M = W_3^T diag(Q) W_3, v = W_3^T R (gwtf_enc_train_mform below: M's fragment images and v in mconst).
- *   gwtf_enc_train_top_scatter   coef [B][512] (times scale [512] when given: coef = gp, scale = s) -> slot_of [B][N] (row of a point, or -1) and
- *                                extra [B][512][256]: row r of shape b = sum of coef[b][c] W_3[c][:] over the channels whose
- *                                arg-max is that point (only the used rows are written); tables: B (2 * 512 + 2) ints of scratch
- *   gwtf_enc_train_backward_top  dA2 (256 channels, tiled) = (M a_2 + v + extra) masked by a_2 > 0; mconst = v [256] | {2^-k};
- *                                sums [64][3][256] += {sum gm_2, sum gm_2 yhat_2, sum a_2}; gmax2[0] = max |dA2|;
- *                                a2rows [B][512][256] (out): row slot_of[b][n] of shape b = a_2(b, :, n) of every arg-max point n,
- *                                point-major (the kernel has them in registers; other rows are not written) */
-int gwtf_enc_train_top_scatter(const float* coef, const float* scale, const int* amax, const float* W3, float* extra, int* slot_of,
-                               int* tables, int B, int N, void* stream);
-int gwtf_enc_train_backward_top(const float* y2, const float* aff2, const float* units_m, const float* mconst, const float* extra,
-                                const int* slot_of, float* dA2, float* sums, float* gmax2, float* a2rows, int B, int N, void* stream);
-/* layer = 1, 2: dA_prev (C[layer] channels, tiled) = (W_layer^T dy_layer) masked by a_{layer-1} > 0 (not stored for layer 1), dy from
- * (y_l, up_g = masked dL/da_layer).  y_prev / aff_prev: y_{layer-1} and its aff (layer 1: x, aff_0, and w0 = raw W_0).
- * sums [64][2 (layer 1: 5)][C[layer]] += {sum gm, sum gm yhat (layer 1: , sum gm x_d)} of the layer below;
- * gmax_prev[0] = max |dA_prev| */
-int gwtf_enc_train_backward(int layer, const float* y_l, const float* up_g, const float* bconst, const float* units_bwd,
-                            const float* y_prev, const float* aff_prev, const float* w0, float* dA_prev, float* sums,
-                            float* gmax_prev, int B, int N, void* stream);
-/* layer = 1, 2: dW (C[layer+1], C[layer]) = sum over this rank's points of dy_layer a_{layer-1}^T; partials: scratch of
- * gwtf_enc_train_dw_partial_floats floats; tab_prev = aff_{layer-1} (layer 1: table0, y_prev = x).  N % 4 == 0. */
+/* floats of the scratch the weight-gradient kernels of `layer` = 1..3 leave their per-slice partials in (layer 3: the Gram matrix). */
 size_t gwtf_enc_train_dw_partial_floats(int layer, int B, int N);
-int gwtf_enc_train_dw(int layer, const float* y_l, const float* up_g, const float* bconst, const float* y_prev,
-                      const float* tab_prev, float* partials, float* dW, int B, int N, void* stream);
-/* layer 3 through the Gram matrix: gram (256,256) = sum_p a_2 a_2^T, S (512,256)[c] = sum_b gp[b][c] a_2(b, amax[b][c]) (read from
- * a2rows / slot_of as gwtf_enc_train_backward_top and gwtf_enc_train_top_scatter left them: call those first); then
- * dW_3 = s (.) S + Q (.) (W_3 gram) + R (x) sum_p a_2  (s, Q, R = bconst of layer 3; sum_p a_2 = row 2 of the sums that
- * gwtf_enc_train_backward_top accumulates). */
-int gwtf_enc_train_dw3(const float* gp, const int* amax, const int* slot_of, const float* a2rows, const float* y2, const float* aff2,
-                       float* partials, float* gram, float* S, int B, int N, void* stream);
+/* Everything the pipeline's launches take, one record for both directions (as GwtfTrainCtx is for the decoder stacks).  Every buffer
+ * is caller-owned; "zero" = must be zero on entry; R = 64 statistic replicas; C = {3, 64, 128, 256, 512}; a per-layer array is
+ * indexed by the layer l = 0..3 (BatchNorm l normalises y_l, C[l+1] channels) unless its comment says otherwise.
+ * Data parallel (SyncBatchNorm): a phase leaves this rank's COMPACT sums in the *_c record, the caller sums a copy of it over the
+ * ranks between the phases (the cuts of gwtf_enc_train_phase), and the *_fold / *_r pointer names that copy; on one rank it names the
+ * *_c record itself.  bn.weight / bn.bias gradients and dW_0's moments are always this rank's (*_c). */
+typedef struct GwtfEncTrainCtx {
+  int B, N;                  /* x is (B, 3, N); N % 4 == 0 and N <= 12288 (the arg-max row table of top_scatter lives in LDS) */
+  double n_total;            /* points the statistics cover: B*N summed over all ranks */
+  float momentum[4];         /* of BatchNorm l: running = (1 - m) running + m batch (unbiased var) */
+  const float* x;            /* [B][3][N]  the reference's input tensor */
+  const float* W[4];         /* [C[l+1]][C[l]]  SharedDot weights */
+  const float* gamma[4];     /* [C[l+1]]  bn.weight */
+  const float* beta[4];      /* [C[l+1]]  bn.bias */
+  float* running_mean[4];    /* [C[l+1]]  updated by the fold of layer l; NULL (both): skip */
+  float* running_var[4];
+  float* mom;                /* [R][12]  zero: += {sum x (3), sum x x^T (xx xy xz yy yz zz), -} over this rank's points (FWD_INIT) */
+  float* mom_c;              /* [12]  the R copies summed (FWD_INIT); read by dw0_finish (this rank's moments) */
+  const float* mom_fold;     /* [12]  what fold0 reads: mom_c, or its copy summed over the ranks */
+  float* sums[3];            /* index l-1, l = 1..3: [R][2][C[l+1]]  zero: += {sum y_l, sum y_l^2} by the forward kernel of layer l */
+  float* sums_c[3];          /* index l-1: [2][C[l+1]]  the R copies summed, behind that kernel */
+  const float* sums_fold[3]; /* index l-1: what the fold of layer l reads: sums_c, or its copy summed over the ranks */
+  float* ymax;               /* [4]  zero: ymax[l] = max |y_l|, l = 1..3 (bit pattern max; the backward's operand scale) */
+  unsigned long long* kmax;  /* [B][512]  zero: 64-bit arg-max key of y_3 per (shape, channel), channels with gamma[3] >= 0 -- layer 3 stores */
+  unsigned long long* kmin;  /* [B][512]  zero: arg-min key, channels with gamma[3] < 0 -- no y: BatchNorm + ReLU is monotone in y per channel */
+  float* aff[4];             /* [4][C[l+1]] = s, t, mean, rstd of BatchNorm l (a = relu(s y + t)), written by its fold; non-finite
+                              * statistics in aff[l-1] or here poison all of aff[l] with NaN */
+  float* table0;             /* [64][4] = (s W_0 row, t): layer 0 folded into layer 1's prologue (fold0) */
+  float* units_f[3];         /* index l-1: gwtf_enc_train_units_floats(l)  MFMA fragment images of W_l (forward) ... */
+  float* units_b[3];         /* ... and of W_l^T (backward), all six from one launch */
+  float* y[2];               /* index l-1, l = 1, 2: gwtf_enc_train_act_floats(B, C[l+1], N)  y_l = W_l . relu(s in + t), tiled */
+  float* pooled;             /* [B][512] = max_n relu(s y_3 + t) from the keys; NaN where a statistic or the extreme is not finite */
+  int* amax;                 /* [B][512]  its first arg-max */
+  float* ystar;              /* [B][512]  y_3 there */
+  /* backward only */
+  const float* g_pooled;     /* [B][512]  dL/d pooled */
+  float* gp;                 /* [B][512] = g_pooled where pooled > 0 (BWD_TOP) */
+  float* gmax;               /* [4]  zero: gmax[l] = max |dL/da_l| masked, l = 1..3 (gmax[3]: max |gp|) */
+  float* g_sums[3];          /* index l = 0..2: [R][5][64], [R][2][128], [R][3][256]  zero: += {sum gm_l, sum gm_l yhat_l} (then l = 0: sum gm x_d,
+                              * 3 rows; l = 2: sum a_2) by the backward kernel of layer l + 1 */
+  float* g_sums_c[4];        /* l = 0..2: [5][64], [2][128], [3][256]  the R copies summed, behind that kernel; l = 3: [2][512] = {sum gp,
+                              * sum gp yhat*} written by BWD_TOP.  Rows 1 / 0 are this rank's bn.weight / bn.bias gradients */
+  const float* g_sums_r[4];  /* [2][C[l+1]]  what the consts kernel of layer l reads: g_sums_c[l], or a copy of its first two rows summed over the ranks */
+  float* bconst[4];          /* [3][C[l+1]] + 4: dy = s gm + Q y + R per channel, then {up, down} = the power-of-two operand scale */
+  float* units_m;            /* gwtf_enc_train_units_floats(3) / 2  fragment images of M 2^k (gwtf_enc_train_mform) */
+  float* mconst;             /* [256 + 4] = {W_3^T R, 2^-k, 0, 0, 0} */
+  float* mform_ws;           /* gwtf_enc_train_mform_workspace_floats(256) scratch */
+  float* extra;              /* [B][512][256]  row r of shape b = sum of gp[b][c] s[c] W_3[c][:] over the channels whose arg-max is that point
+                              * (only the used rows are written) */
+  int* slot_of;              /* [B][N]  row of a point, or -1 */
+  int* tables;               /* [B (2 * 512 + 2)] scratch of top_scatter */
+  float* a2rows;             /* [B][512][256]  row slot_of[b][n] of shape b = a_2(b, :, n) of every arg-max point n (other rows not written) */
+  float* dA[2];              /* index l-1, l = 1, 2: gwtf_enc_train_act_floats(B, C[l+1], N)  dL/da_l masked by a_l > 0, tiled; dA[1] =
+                              * (M a_2 + v + extra) by the top layer, dA[0] = W_2^T dy_2 by layer 2 (layer 1 stores none) */
+  float* partials;           /* max over l = 1..3 of gwtf_enc_train_dw_partial_floats(l, B, N) scratch */
+  float* gram;               /* [256][256] = sum_p a_2 a_2^T over this rank's points */
+  float* S;                  /* [512][256]  S[c] = sum_b gp[b][c] a_2(b, amax[b][c]) */
+  float* dW[4];              /* [C[l+1]][C[l]]  the weight gradients over this rank's points */
+  void* stream;
+} GwtfEncTrainCtx;
+/* The chain is cut where a data-parallel run sums the statistics over the ranks: the record named behind a phase goes into what *_fold / *_r names:
+ *   FWD_INIT      xmoments, compact                                                     -> mom_c
+ *   FWD_LAYER l   l = 0: fold0, pack_all; l = 1..3: fold of layer l; then l < 3: forward kernel of layer l + 1, compact
+ *                 -> sums_c[l]; l = 3: pool
+ *   BWD_TOP       top                                                                   -> g_sums_c[3]
+ *   BWD_LAYER l   consts of layer l, then  l = 3: mform, top_scatter, backward_top (M form: dL/da_2 = M a_2 + v + extra, M = W_3^T diag(Q)
+ *                 W_3, v = W_3^T R), compact, dw3 (Gram form), dw3_finish;  l = 2, 1: backward, dw, compact;  l = 0: dw0_finish
+ *                 -> g_sums_c[l - 1][0..2)
+ * gwtf_enc_train_forward / _backward are the loops over the phases.  GWTF_E_BADARG without a launch: a NULL record, B or N <= 0,
+ * N % 4 != 0, N * sizeof(int) > 48 KiB, n_total <= 0, a NULL field other than running_mean / running_var (the backward fields only
+ * for a backward phase), a phase or layer out of range. */
+#define GWTF_ENC_PHASE_FWD_INIT 0
+#define GWTF_ENC_PHASE_FWD_LAYER 1
+#define GWTF_ENC_PHASE_BWD_TOP 2
+#define GWTF_ENC_PHASE_BWD_LAYER 3
+int gwtf_enc_train_phase(const GwtfEncTrainCtx* ctx, int phase, int layer);
+int gwtf_enc_train_forward(const GwtfEncTrainCtx* ctx);
+int gwtf_enc_train_backward(const GwtfEncTrainCtx* ctx);
 /* The small dense algebra between those kernels (csrc/gwtf_encoder_glue.hip), a launch or two each instead of chains of library calls:
  *   gwtf_stat_compact          out [n] = sum of the `replicas` copies of slab [replicas][n], fixed order
  *   gwtf_enc_train_mform       bconst3 = {s, Q, R} [3][C4] of layer 3 -> units_m = fragment images of M 2^k (M = W_3^T diag(Q) W_3,
- *                              k = 8 - floor(log2 max|M|)), mconst [C3 + 4] = {W_3^T R, 2^-k, 0, 0, 0}: what gwtf_enc_train_backward_top
+ *                              k = 8 - floor(log2 max|M|)), mconst [C3 + 4] = {W_3^T R, 2^-k, 0, 0, 0}: what the top layer's backward kernel
  *                              reads.  workspace: gwtf_enc_train_mform_workspace_floats(C3) floats.  C3 % 32 == 0, C4 % 64 == 0.
  *   gwtf_enc_train_dw3_finish  dW_3 [C4][C3] = s (.) S + Q (.) (W_3 gram) + R (x) a2sum   (a2sum [C3] = sum_p a_2)
  *   gwtf_enc_train_dw0_finish  dW_0 [C1][3] = s (.) red5[2:5]^T + Q (.) (W_0 Mxx) + R (x) m[:3]; bconst0 = {s, Q, R} [3][C1] of layer 0,
- *                              red5 [5][C1] = the compact sums of gwtf_enc_train_backward(layer 1), mom12 = this rank's coordinate
- *                              moments (gwtf_enc_train_xmoments, compact) */
+ *                              red5 [5][C1] = the compact sums the backward kernel of layer 1 leaves (g_sums_c[0]), mom12 = this rank's coordinate
+ *                              moments (mom_c) */
 int gwtf_stat_compact(const float* slab, float* out, int replicas, int n, void* stream);
 size_t gwtf_enc_train_mform_workspace_floats(int C3);
 int gwtf_enc_train_mform(const float* W3, const float* bconst3, float* workspace, float* units_m, float* mconst, int C3, int C4,

@@ -59,28 +59,76 @@ def test_library_loads_and_exports_every_declared_symbol():
 
 
 def _c_struct_fields(header, name):
-    """[(field, kind)] of `typedef struct <name> { ... } <name>;` in declaration order; kind: pointer / int / float / double / size_t."""
+    """[(field, kind)] of `typedef struct <name> { ... } <name>;` in declaration order; kind: pointer / int / float / double / size_t,
+    with `[n]` behind it for an array field `name[n]`."""
     body = re.search(r'typedef struct %s \{(.*?)\} %s;' % (name, name), header, re.S).group(1)
     body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
     fields = []
     for decl in filter(None, (d.strip() for d in body.split(';'))):
-        ctype, names = re.fullmatch(r'((?:const\s+)?(?:unsigned\s+)?\w+(?:\s*\*)?)\s*(\w+(?:\s*,\s*\w+)*)', decl).groups()
+        ctype, names = re.fullmatch(r'((?:const\s+)?(?:unsigned\s+)?(?:long\s+)?\w+(?:\s*\*)?)\s*(\w+(?:\[\d+\])?(?:\s*,\s*\w+(?:\[\d+\])?)*)',
+                                    decl).groups()
         kind = 'pointer' if '*' in ctype else ctype
         assert kind in ('pointer', 'int', 'float', 'double', 'size_t'), decl
-        fields += [(n.strip(), kind) for n in names.split(',')]
+        for n in names.split(','):
+            field, dim = re.fullmatch(r'(\w+)(\[\d+\])?', n.strip()).groups()
+            fields.append((field, kind + (dim or '')))
     return fields
 
 
-def test_ctypes_records_follow_the_header_field_for_field():
-    """_lib.StackArgs / _lib.TrainCtx are hand-written mirrors of GwtfStackArgs / GwtfTrainCtx: same names, same order, same kind of
-    C type -- a transposed or missing field would bind and load without complaint and shift every field behind it."""
-    header = open(os.path.join(ROOT, 'include', 'gwtf.h')).read()
+def _mirror_fields(mirror):
     kinds = {ctypes.c_int: 'int', ctypes.c_float: 'float', ctypes.c_double: 'double', ctypes.c_size_t: 'size_t',
              ctypes.c_void_p: 'pointer', ctypes.POINTER(ctypes.c_int): 'pointer'}
-    for c_name, mirror in (('GwtfStackArgs', _lib.StackArgs), ('GwtfTrainCtx', _lib.TrainCtx)):
+    return [(n, f'{kinds[t._type_]}[{t._length_}]' if issubclass(t, ctypes.Array) else kinds[t]) for n, t in mirror._fields_]
+
+
+def test_ctypes_records_follow_the_header_field_for_field():
+    """The records of _lib are hand-written mirrors of the structs of include/gwtf.h: same names, same order, same kind of C type,
+    same array lengths -- a transposed or missing field would bind and load without complaint and shift every field behind it.
+    The minimum field count of each record guards the header parser itself (a struct it reads only in part)."""
+    header = open(os.path.join(ROOT, 'include', 'gwtf.h')).read()
+    for c_name, mirror, at_least in (('GwtfStackArgs', _lib.StackArgs, 22), ('GwtfTrainCtx', _lib.TrainCtx, 43),
+                                     ('GwtfEncTrainCtx', _lib.EncTrainCtx, 47), ('GwtfCloudArgs', _lib.CloudArgs, 31),
+                                     ('GwtfRouteArgs', _lib.RouteArgs, 20), ('GwtfRoutedStackArgs', _lib.RoutedStackArgs, 17)):
         declared = _c_struct_fields(header, c_name)
-        assert len(declared) > 20, c_name
-        assert [(n, kinds[t]) for n, t in mirror._fields_] == declared, c_name
+        assert len(declared) >= at_least, c_name
+        assert _mirror_fields(mirror) == declared, c_name
+
+
+def test_encoder_train_record_is_validated_before_anything_is_launched():
+    """gwtf_enc_train_phase / _forward / _backward refuse (GWTF_E_BADARG, host only) a NULL record, bad sizes, a NULL required field
+    and a phase or layer out of range."""
+    L = _lib.lib()
+    E = 10001
+
+    def record(**over):
+        t = _lib.EncTrainCtx(B=2, N=36, n_total=72.0)
+        for name, ctype in t._fields_:                     # every pointer set: the address is never read by the validation
+            if ctype is ctypes.c_void_p and name != 'stream':
+                setattr(t, name, 0x1000)
+            elif issubclass(ctype, ctypes.Array) and ctype._type_ is ctypes.c_void_p:
+                getattr(t, name)[:] = [0x1000] * ctype._length_
+        for name, value in over.items():
+            if isinstance(value, tuple):
+                getattr(t, name)[value[0]] = value[1]
+            else:
+                setattr(t, name, value)
+        return t
+
+    calls = (lambda a: L.gwtf_enc_train_phase(a, _lib.ENC_PHASE_FWD_INIT, 0), L.gwtf_enc_train_forward,
+             lambda a: L.gwtf_enc_train_phase(a, _lib.ENC_PHASE_BWD_TOP, 0), L.gwtf_enc_train_backward)
+    for call in calls:
+        assert call(None) == E
+        for bad in (dict(B=0), dict(N=6), dict(N=12292), dict(n_total=0.0), dict(x=None), dict(aff=(2, None)), dict(pooled=None)):
+            assert call(ctypes.addressof(record(**bad))) == E, bad
+    for call in calls[2:]:
+        assert call(ctypes.addressof(record(g_pooled=None))) == E
+        assert call(ctypes.addressof(record(dW=(3, None)))) == E
+    ok = record()
+    assert L.gwtf_enc_train_phase(ctypes.addressof(ok), 99, 0) == E
+    assert L.gwtf_enc_train_phase(ctypes.addressof(ok), -1, 0) == E
+    assert L.gwtf_enc_train_phase(ctypes.addressof(ok), _lib.ENC_PHASE_FWD_LAYER, 4) == E
+    assert L.gwtf_enc_train_phase(ctypes.addressof(ok), _lib.ENC_PHASE_BWD_LAYER, 4) == E
+    assert L.gwtf_enc_train_phase(ctypes.addressof(ok), _lib.ENC_PHASE_BWD_LAYER, -1) == E
 
 
 def test_buffer_sizes_and_raw_arena_layout():
