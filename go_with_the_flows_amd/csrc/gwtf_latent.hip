@@ -5,6 +5,9 @@
 //     pnll = sum_b nll_b / B            loss = pw pnll + gw gnll - ew gent
 // As torch ops these are ~25 elementwise / reduction launches forward and ~30 backward on (B, G) tensors of a few thousand elements:
 // 0.15 ms of a 9 ms step spent on launch latency.
+// Two families: the base Gaussian shared by the batch (mu0, lv0 [G]: the generative / autoencoding models' learned parameters) and
+// one base Gaussian per row (mu0, lv0 [B][G]: the single-view reconstruction model's g0_prior(img_encoder(images))); the `rows`
+// family reads mu0[e] / lv0[e] where the shared one reads mu0[e % G], and its backward has no column sums.
 #include <hip/hip_runtime.h>
 #include "../../include/gwtf.h"
 
@@ -25,6 +28,7 @@ __device__ __forceinline__ float block_sum(float v, float* red, int tid) {
 
 // stage 1: one element per thread (the n2 flow_lv loads of a thread are independent and coalesced across the wave);
 // part[blk] = {sum of the gnll integrand, sum of post_lv} of the block's 256 elements
+template <bool kRows>
 __global__ __launch_bounds__(kThreads) void latent_part_kernel(const float* __restrict__ z, const float* __restrict__ mu0,
                                                                const float* __restrict__ lv0, const float* __restrict__ flow_lv,
                                                                const float* __restrict__ post_lv, float2* __restrict__ part, int B,
@@ -33,7 +37,7 @@ __global__ __launch_bounds__(kThreads) void latent_part_kernel(const float* __re
   const int tid = threadIdx.x, n = B * G, e = blockIdx.x * kThreads + tid;
   float sg = 0.f, se = 0.f;
   if (e < n) {
-    const int j = e % G;
+    const int j = kRows ? e : e % G;                   // the element's base Gaussian: its own, or its column's
     const float d = z[e] - mu0[j], l0 = lv0[j];
     float s0 = 0.f, s1 = 0.f;
     int l = 0;
@@ -111,6 +115,34 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(const float* __restrict
   g_lv0[j] = 0.5f * cg * ((float)B - r * sl);
 }
 
+// per-row base: every gradient is elementwise (mu0 / lv0 have the shape of z), one element per thread
+__global__ __launch_bounds__(256) void latent_rows_bwd_kernel(const float* __restrict__ g_out, const float* __restrict__ z,
+                                                              const float* __restrict__ mu0, const float* __restrict__ lv0,
+                                                              float* __restrict__ g_nll, float* __restrict__ g_z,
+                                                              float* __restrict__ g_mu0, float* __restrict__ g_lv0,
+                                                              float* __restrict__ g_flow, float* __restrict__ g_post, int B, int G,
+                                                              int n2, float pw, float gw, float ew) {
+  const float gl = g_out[0];
+  const float cp = (gl * pw + g_out[1]) / (float)B, cg = (gl * gw + g_out[2]) / (float)B, ce = (g_out[3] - gl * ew) / (float)B;
+  const int n = B * G, e = blockIdx.x * 256 + threadIdx.x;
+  if (e < B) g_nll[e] = cp;
+  if (e >= n) return;
+  const float d = z[e] - mu0[e], r = __expf(-lv0[e]);
+  const float gz = cg * d * r;
+  g_z[e] = gz;
+  g_mu0[e] = -gz;
+  g_lv0[e] = 0.5f * cg * (1.0f - r * d * d);
+  g_post[e] = 0.5f * ce;
+  const float c = 0.5f * cg;
+  for (int l = 0; l < n2; ++l) g_flow[(size_t)l * n + e] = c;
+}
+
+// B * G elements in blocks of kThreads: 0 when the product does not fit an int (the element index of the kernels)
+int latent_blocks(int B, int G) {
+  const long long n = (long long)B * G;
+  return n > 0x7fffffffLL - kThreads ? 0 : (int)((n + kThreads - 1) / kThreads);
+}
+
 }  // namespace
 
 extern "C" int gwtf_latent_loss_workspace_floats(int B, int G) { return 2 * ((B * G + kThreads - 1) / kThreads); }
@@ -120,7 +152,7 @@ extern "C" int gwtf_latent_loss_forward(const float* nll, const float* z, const 
                                         float ew, void* stream) {
   if (!nll || !z || !mu0 || !lv0 || !flow_lv || !post_lv || !workspace || !out4 || B <= 0 || G <= 0 || n2 <= 0) return GWTF_E_BADARG;
   const int nb = (B * G + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(latent_part_kernel, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, z, mu0, lv0, flow_lv, post_lv,
+  hipLaunchKernelGGL(latent_part_kernel<false>, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, z, mu0, lv0, flow_lv, post_lv,
                      (float2*)workspace, B, G, n2);
   hipLaunchKernelGGL(latent_finish_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, nll, (const float2*)workspace, out4, B, G,
                      nb, pw, gw, ew);
@@ -135,5 +167,31 @@ extern "C" int gwtf_latent_loss_backward(const float* g_out4, const float* z, co
   const int nb_e = (B * G + 255) / 256, nb_c = (G + 255) / 256;
   hipLaunchKernelGGL(latent_bwd_kernel, dim3(nb_e + nb_c), dim3(256), 0, (hipStream_t)stream, g_out4, z, mu0, lv0, g_nll, g_z, g_mu0,
                      g_lv0, g_flow_lv, g_post_lv, B, G, n2, pw, gw, ew, nb_e);
+  return (int)hipGetLastError();
+}
+
+// ---- one base Gaussian per row: mu0, lv0 (and their gradients) are [B][G] ---------------------------------------------------------------
+extern "C" int gwtf_latent_loss_rows_forward(const float* nll, const float* z, const float* mu0, const float* lv0, const float* flow_lv,
+                                             const float* post_lv, float* workspace, float* out4, int B, int G, int n2, float pw,
+                                             float gw, float ew, void* stream) {
+  if (!nll || !z || !mu0 || !lv0 || !flow_lv || !post_lv || !workspace || !out4 || B <= 0 || G <= 0 || n2 <= 0) return GWTF_E_BADARG;
+  const int nb = latent_blocks(B, G);
+  if (nb == 0) return GWTF_E_BADARG;
+  hipLaunchKernelGGL(latent_part_kernel<true>, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, z, mu0, lv0, flow_lv, post_lv,
+                     (float2*)workspace, B, G, n2);
+  hipLaunchKernelGGL(latent_finish_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, nll, (const float2*)workspace, out4, B, G,
+                     nb, pw, gw, ew);
+  return (int)hipGetLastError();
+}
+
+extern "C" int gwtf_latent_loss_rows_backward(const float* g_out4, const float* z, const float* mu0, const float* lv0, float* g_nll,
+                                              float* g_z, float* g_mu0, float* g_lv0, float* g_flow_lv, float* g_post_lv, int B, int G,
+                                              int n2, float pw, float gw, float ew, void* stream) {
+  if (!g_out4 || !z || !mu0 || !lv0 || !g_nll || !g_z || !g_mu0 || !g_lv0 || !g_flow_lv || !g_post_lv || B <= 0 || G <= 0 || n2 <= 0)
+    return GWTF_E_BADARG;
+  const int nb = latent_blocks(B, G);
+  if (nb == 0) return GWTF_E_BADARG;
+  hipLaunchKernelGGL(latent_rows_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, g_out4, z, mu0, lv0, g_nll, g_z, g_mu0, g_lv0,
+                     g_flow_lv, g_post_lv, B, G, n2, pw, gw, ew);
   return (int)hipGetLastError();
 }

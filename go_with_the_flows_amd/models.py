@@ -13,7 +13,9 @@ the encoder (fused HIP kernel in eval), the prior flow, ONE batched launch for t
 The image-conditioned variant, Flow_Mixture_SVR_Model (flow_mixture.py:181-230, single-view reconstruction), is mirrored the
 same way: its 4-channel ResNet-18 image encoder (resnet.py) runs on the HIP kernels of csrc/gwtf_resnet.hip in eval mode and
 on the library modules in train mode; the image's features give the prior flow its per-shape base Gaussian (``g0_prior``).
-``reconstruct_many`` is its batched evaluation path (S images -> S clouds, one partitioned decoder launch).
+``reconstruct_many`` is its batched evaluation path (S images -> S clouds, one partitioned decoder launch); its
+``forward_fused(g, p, warmup, images=...)`` is the training path (the loss then reduces the latent terms against the per-image base
+Gaussian in one launch, prior.LatentLossRowsFn), which ``training.GraphedTrainStep(..., images_example=...)`` captures.
 """
 import math
 import os
@@ -322,7 +324,11 @@ class Flow_Mixture_Model(Local_Cond_RNVP_MC_Global_RNVP_VAE):
         eval mode and no gradient is needed; per component otherwise)."""
         if self.mode != 'training':
             raise ValueError("forward_fused is the density ('training') pass; use sample_fused for generation")
-        output_encoder = self.encode(g_input, defer_prior=True)     # the prior flow runs beside the decoders (side stream)
+        # the prior flow runs beside the decoders (side stream)
+        return self._fused_after_encode(self.encode(g_input, defer_prior=True), p_input, warmup)
+
+    def _fused_after_encode(self, output_encoder, p_input, warmup):
+        """forward_fused behind the encoder: mixture weights, the decoders' base Gaussian, the K decoders, the prior flow joined."""
         g_sample = output_encoder['g_posterior_samples']
         logits = self.get_weights(g_sample, warmup)
         B, K, P = g_sample.shape[0], self.n_components, self.p_latent_space_size
@@ -455,9 +461,11 @@ class Flow_Mixture_SVR_Model(Flow_Mixture_Model):
         self.g0_prior_mus = None
         self.g0_prior_logvars = None
 
-    def encode(self, g_input, images, defer_prior=False):
-        """flow_mixture.py:199-230 -> the encoder dict; lists are ordered base -> data.  No '_g0_params': the base is per row, so
-        the loss takes its list path (the fused latent-loss kernel assumes one base Gaussian for the batch)."""
+    def encode(self, g_input, images, defer_prior=False, fused_base=False):
+        """flow_mixture.py:199-230 -> the encoder dict; lists are ordered base -> data.  No '_g0_params': the base is per row.
+        fused_base=True (forward_fused): the per-row base Gaussian is also handed over as out['_g0_rows'] = (mus, logvars), the
+        tensors of g_prior_mus[0] / g_prior_logvars[0], and the loss reduces its latent terms in one launch
+        (prior.LatentLossRowsFn); without it the loss takes its list path."""
         if images is None:
             raise ValueError('Flow_Mixture_SVR_Model.encode needs images')
         if self.mode not in ('training', 'reconstruction'):
@@ -466,6 +474,8 @@ class Flow_Mixture_SVR_Model(Flow_Mixture_Model):
         out = {}
         mus, logvars = self.g0_prior(self.img_encoder(images))
         out['g_prior_mus'], out['g_prior_logvars'] = [mus], [logvars]
+        if fused_base:
+            out['_g0_rows'] = (mus, logvars)
         if self.mode == 'training':
             out['g_posterior_mus'], out['g_posterior_logvars'] = self.g_posterior(self._pooled_features(g_input))
             out['g_posterior_samples'] = self.reparameterize(out['g_posterior_mus'], out['g_posterior_logvars'])
@@ -501,8 +511,14 @@ class Flow_Mixture_SVR_Model(Flow_Mixture_Model):
         output_decoder, logits = self.decode(p_input, g_sample, size, labeled_samples, warmup)
         return self.finish_encode(output_encoder), output_decoder, logits
 
-    def forward_fused(self, g_input, p_input, warmup=False):
-        raise NotImplementedError('Flow_Mixture_SVR_Model trains through forward + Flow_Mixture_Loss (the list path)')
+    def forward_fused(self, g_input, p_input, warmup=False, images=None):
+        """Flow_Mixture_Model.forward_fused with the image branch: the base class's body behind the SVR encoder, whose per-row
+        base Gaussian reaches ``Flow_Mixture_Loss.fused`` as '_g0_rows'.  -> (output_encoder, dec)."""
+        if self.mode != 'training':
+            raise ValueError("forward_fused is the density ('training') pass; use reconstruct_many for reconstruction")
+        if images is None:
+            raise ValueError('Flow_Mixture_SVR_Model.forward_fused needs images')
+        return self._fused_after_encode(self.encode(g_input, images, defer_prior=True, fused_base=True), p_input, warmup)
 
     @torch.no_grad()
     def reconstruct_many(self, images, n_points, return_labels=False, state=None):
@@ -586,17 +602,25 @@ class Flow_Mixture_Loss(nn.Module):
         return self.pnll_weight * pnll + self.gnll_weight * gnll - self.gent_weight * gent, pnll, gnll, gent
 
     def _combine_fused(self, nll, output_prior):
-        """All four values in one launch (prior.LatentLossFn) when the prior flow handed its logvars over as one tensor."""
-        flow_lv, g0 = output_prior.get('_g_prior_logvars_stacked'), output_prior.get('_g0_params')
+        """All four values in one launch when the prior flow handed its logvars over as one tensor: prior.LatentLossFn with the
+        batch's one base Gaussian ('_g0_params'), prior.LatentLossRowsFn with a base Gaussian per row ('_g0_rows')."""
+        flow_lv, g0, rows = output_prior.get('_g_prior_logvars_stacked'), output_prior.get('_g0_params'), False
+        if g0 is None:
+            g0, rows = output_prior.get('_g0_rows'), True
         post_lv, z = output_prior.get('g_posterior_logvars'), output_prior['g_prior_samples'][0]
         if flow_lv is None or g0 is None or post_lv is None or os.environ.get('GWTF_NO_FUSED_LATENT_LOSS') == '1':
             return None
         ts = (nll, z, g0[0], g0[1], flow_lv, post_lv)
         if not all(t.is_cuda and t.dtype == torch.float32 for t in ts) or z.dim() != 2:
             return None
-        from .prior import LatentLossFn
-        vals = LatentLossFn.apply(nll.contiguous(), z.contiguous(), g0[0].reshape(-1), g0[1].reshape(-1), flow_lv.contiguous(),
-                                  post_lv.contiguous(), float(self.pnll_weight), float(self.gnll_weight), float(self.gent_weight))
+        from . import prior
+        w = (float(self.pnll_weight), float(self.gnll_weight), float(self.gent_weight))
+        if rows:
+            vals = prior.LatentLossRowsFn.apply(nll.contiguous(), z.contiguous(), g0[0].contiguous(), g0[1].contiguous(),
+                                                flow_lv.contiguous(), post_lv.contiguous(), *w)
+        else:
+            vals = prior.LatentLossFn.apply(nll.contiguous(), z.contiguous(), g0[0].reshape(-1), g0[1].reshape(-1),
+                                            flow_lv.contiguous(), post_lv.contiguous(), *w)
         return vals[0], vals[1], vals[2], vals[3]
 
     def forward(self, output_prior, output_decoder, mixture_weights_logits):

@@ -362,6 +362,47 @@ class LatentLossFn(torch.autograd.Function):
         return g_nll, g_z.view(B, G), g_mu0, g_lv0, g_flow.view(n2, B, G), g_post.view(B, G), None, None, None
 
 
+class LatentLossRowsFn(torch.autograd.Function):
+    """LatentLossFn with one base Gaussian PER ROW: mu0, lv0 (B, G) -- the single-view reconstruction model's
+    g0_prior(img_encoder(images)).  Same four values, one HIP launch forward and one (elementwise) backward."""
+
+    @staticmethod
+    def forward(ctx, nll, z, mu0, lv0, flow_lv, post_lv, pw, gw, ew):
+        from . import _lib
+        B, G = z.shape if z.dim() == 2 else (-1, -1)
+        n2 = flow_lv.shape[0] if flow_lv.dim() == 3 else -1
+        if (min(B, G, n2) < 1 or nll.shape != (B,) or mu0.shape != (B, G) or lv0.shape != (B, G) or flow_lv.shape != (n2, B, G)
+                or post_lv.shape != (B, G)):
+            raise _lib.GwtfError(f'latent loss (per-row base): shapes {tuple(nll.shape)} {tuple(z.shape)} {tuple(mu0.shape)} '
+                                 f'{tuple(lv0.shape)} {tuple(flow_lv.shape)} {tuple(post_lv.shape)} are not (B,), (B,G), (B,G), (B,G), '
+                                 f'(n2,B,G), (B,G)')
+        L, P = _lib.lib(), _lib._ptr
+        ws = L.gwtf_latent_loss_workspace_floats(B, G)
+        buf = torch.empty(ws + 4, device=z.device, dtype=torch.float32)
+        out = buf[ws:]
+        _lib.check(L.gwtf_latent_loss_rows_forward(P(nll, 'nll'), P(z, 'z'), P(mu0, 'mu0'), P(lv0, 'lv0'), P(flow_lv, 'flow_lv'),
+                                                   P(post_lv, 'post_lv'), buf.data_ptr(), out.data_ptr(), B, G, n2, pw, gw, ew,
+                                                   _lib._stream(z)))
+        ctx.save_for_backward(z, mu0, lv0)
+        ctx.cfg = (B, G, n2, pw, gw, ew)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        from . import _lib
+        z, mu0, lv0 = ctx.saved_tensors
+        B, G, n2, pw, gw, ew = ctx.cfg
+        g_out = g_out.contiguous()
+        buf = torch.empty(B + (n2 + 4) * B * G, device=z.device, dtype=torch.float32)
+        g_nll, g_z, g_post, g_mu0, g_lv0, g_flow = buf.split([B, B * G, B * G, B * G, B * G, n2 * B * G])
+        _lib.check(_lib.lib().gwtf_latent_loss_rows_backward(_lib._ptr(g_out, 'g_out'), z.data_ptr(), mu0.data_ptr(), lv0.data_ptr(),
+                                                             g_nll.data_ptr(), g_z.data_ptr(), g_mu0.data_ptr(), g_lv0.data_ptr(),
+                                                             g_flow.data_ptr(), g_post.data_ptr(), B, G, n2, pw, gw, ew,
+                                                             _lib._stream(z)))
+        return (g_nll, g_z.view(B, G), g_mu0.view(B, G), g_lv0.view(B, G), g_flow.view(n2, B, G), g_post.view(B, G), None, None,
+                None)
+
+
 class GaussianFlowNLL(nn.Module):
     """reference losses.py:24-33: 0.5 * (sum(sum_j logvars_j + (z - mu0)^2 / exp(logvar0)) / B + G log 2 pi)."""
 

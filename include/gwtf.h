@@ -143,6 +143,15 @@ int gwtf_latent_loss_forward(const float* nll, const float* z, const float* mu0,
 int gwtf_latent_loss_backward(const float* g_out4, const float* z, const float* mu0, const float* lv0, float* g_nll, float* g_z,
                               float* g_mu0, float* g_lv0, float* g_flow_lv, float* g_post_lv, int B, int G, int n2, float pw, float gw,
                               float ew, void* stream);
+/* The same four values with ONE BASE GAUSSIAN PER ROW: mu0, lv0 [B][G] (single-view reconstruction: g0_prior(img_encoder(images))), and
+ * g_mu0, g_lv0 [B][G] in the backward, which is elementwise throughout.  Every other argument, the workspace size
+ * (gwtf_latent_loss_workspace_floats) and the two-stage block-ordered reduction (no float atomics: same inputs, same bits) as above. */
+int gwtf_latent_loss_rows_forward(const float* nll, const float* z, const float* mu0, const float* lv0, const float* flow_lv,
+                                  const float* post_lv, float* workspace, float* out4, int B, int G, int n2, float pw, float gw,
+                                  float ew, void* stream);
+int gwtf_latent_loss_rows_backward(const float* g_out4, const float* z, const float* mu0, const float* lv0, float* g_nll, float* g_z,
+                                   float* g_mu0, float* g_lv0, float* g_flow_lv, float* g_post_lv, int B, int G, int n2, float pw,
+                                   float gw, float ew, void* stream);
 /* Tile plan of a forward launch (what stack_dispatch decides; diagnostic + tests): out[0] = points per wavefront of the main
  * launch, out[1] = its workgroups, out[2] = points per wavefront of the tail launch (0: none), out[3] = its workgroups.
  * The choice minimises resident rounds x the cost of a round of that tile (calibrated, csrc/gwtf_stack.hip tile_cost). */
