@@ -39,6 +39,7 @@ _SIGNATURES = {
     'gwtf_latent_loss_rows_forward': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 3 + [ctypes.c_float] * 3 + [_c_fp]),
     'gwtf_latent_loss_rows_backward': (ctypes.c_int, [_c_fp] * 10 + [ctypes.c_int] * 3 + [ctypes.c_float] * 3 + [_c_fp]),
     'gwtf_stack_plan': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]),
+    'gwtf_bwd_plan': (ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_int)]),
     'gwtf_pack_w1t': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_fp]),
     'gwtf_packed_b_coupling_floats': (ctypes.c_size_t, [ctypes.c_int]),
     'gwtf_pack_folded': (ctypes.c_int, [_c_fp] * 5 + [ctypes.c_int, ctypes.c_int, _c_fp]),

@@ -21,13 +21,12 @@
 // transposed.  Each wavefront owns one column of 16x16 output tiles over ALL points of the workgroup (no cross-wave
 // reduction), and writes it to a per-workgroup partial that gwtf_dw1_reduce sums in a fixed order: nothing of size
 // O(B N f) is written to HBM any more (it was 100-150 MB per coupling).
+// Host side: bwd_plan decides variant, tile and grid from the shape alone (gwtf_bwd_plan exports it; the dW1 workspace is sized
+// from the same grid), launch_plan turns a plan and a GwtfBwdArgs record into the one kernel call.
 #include "gwtf_device.h"
 #include "gwtf_dw1.h"
 #include <algorithm>
 
-#ifndef GWTF_K2_MASK
-#define GWTF_K2_MASK 15     // A/B knob: which compile-time-pattern variants the launcher uses (1 / 2: light pass, one warped / one kept; 4 / 8: merged pass)
-#endif
 #ifndef GWTF_BWD_ABLATE
 #define GWTF_BWD_ABLATE 0   // TIMING PROBES of the merged pass (wrong results): 1 no sd0 LDS atomics | 2 no dW1 partial stores | 4 per-wave
                             // scale (no amax barrier) | 8 no dW1 product | 16 no sd0 sums at all | 32 no transposed-dacc stores
@@ -59,7 +58,7 @@ struct BCfg {
 // 0: one kept / two warped; -1: read from `pat`).  With one warped coordinate the second output column of sd2 does not exist: its
 // u_1 terms, its FiLM-record sum (one of three 16-lane reductions + LDS atomics per feature row in the light pass) and the second
 // tail slot fold away -- the train pipeline's launcher picks the variant per level (the pattern is a host-side fact).
-enum { BW_DIRECT = 0, BW_LIGHT = 2, BW_MERGED = 3 };
+enum { BW_DIRECT = GWTF_BWD_PASS_DIRECT, BW_LIGHT = GWTF_BWD_PASS_LIGHT, BW_MERGED = GWTF_BWD_PASS_MERGED };
 // FULL: N is a multiple of the workgroup's tile (no point beyond the cloud: the per-element bound selects of the merged pass fold away).
 template <int MB, int NB, int VAR, int MG = -1, int K2 = -1, bool FULL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 4 ? 2 : (MB <= 3 ? 3 : 1)))) void bwd_kernel(const float* __restrict__ x_in, const float* __restrict__ g_out,
@@ -647,56 +646,102 @@ __global__ void pack_folded_kernel(const float* __restrict__ W1p, const float* _
   }
 }
 
-template <int MB, int VAR>
-int launch_bwd(int nb, const float* x_in, const float* g_out, const float* g_ld, const float* pw_c, const float* pb_c,
-               const float* film, float* g_in, float* dw1_ws, float* g_film, float* g_sd0, float* g_bias,
-               const float* g_stats, int B, int N, int C, int c, int pat, float eps, int kk_steps, int f, int mode, int K,
-               const GwtfKS& ks, const float* g_ps_c, const float* g_lvs_c, const GwtfCombine& cmb, hipStream_t st) {
-  const int pts_wg = 64 * nb;
-  const dim3 grid((unsigned)(B * ((N + pts_wg - 1) / pts_wg)), (unsigned)K), block(256);
-  if constexpr (MB == 3 && (VAR == BW_LIGHT || VAR == BW_MERGED)) {
-    // the train pipeline's two passes at the abs-form widths (f = 33..40): the forward recompute as one basic block (MG = 1)
-    if (gwtf_abs_form(f)) {
-      const bool small_tile_mg = (ks.tune & GWTF_TUNE_SMALL_LIGHT_TILE) != 0;   // per-call diagnostic (tools/diag/light_tile_check.py)
-      if (VAR == BW_LIGHT && nb == 2 && (long)B * N * K >= 256L * 1024 && !small_tile_mg) {
-        // 256-point tiles, and as many of a shape's tiles per workgroup as still leave one full round of 512 resident workgroups
-        const int tps = (N + 255) / 256;
-        GwtfKS k4 = ks;
-        k4.tpw = (int)std::max(1L, std::min((long)tps, (long)B * tps * K / 512));
-        if (ks.tune & GWTF_TUNE_SINGLE_TILE) k4.tpw = 1;
-        const dim3 grid4((unsigned)(B * ((tps + k4.tpw - 1) / k4.tpw)), (unsigned)K);
-        if (pat < 3 && (GWTF_K2_MASK & 1)) hipLaunchKernelGGL((bwd_kernel<MB, 4, VAR, 1, 1>), grid4, block, 0, st, x_in, g_out, g_ld, pw_c, pb_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, g_stats, B, N, C, c, pat, eps, kk_steps, f, mode, k4, g_ps_c, g_lvs_c, cmb);
-        else if (pat >= 3 && (GWTF_K2_MASK & 2)) hipLaunchKernelGGL((bwd_kernel<MB, 4, VAR, 1, 0>), grid4, block, 0, st, x_in, g_out, g_ld, pw_c, pb_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, g_stats, B, N, C, c, pat, eps, kk_steps, f, mode, k4, g_ps_c, g_lvs_c, cmb);
-        else hipLaunchKernelGGL((bwd_kernel<MB, 4, VAR, 1>), grid4, block, 0, st, x_in, g_out, g_ld, pw_c, pb_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, g_stats, B, N, C, c, pat, eps, kk_steps, f, mode, k4, g_ps_c, g_lvs_c, cmb);
-      } else if (nb == 1) {
-        hipLaunchKernelGGL((bwd_kernel<MB, 1, VAR, 1>), grid, block, 0, st, x_in, g_out, g_ld, pw_c, pb_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, g_stats, B, N, C, c, pat, eps, kk_steps, f, mode, ks, g_ps_c, g_lvs_c, cmb);
-      } else if (pat < 3 && (GWTF_K2_MASK & 4) && N % 128 == 0 && VAR == BW_MERGED) {
-        hipLaunchKernelGGL((bwd_kernel<MB, 2, VAR, 1, 1, true>), grid, block, 0, st, x_in, g_out, g_ld, pw_c, pb_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, g_stats, B, N, C, c, pat, eps, kk_steps, f, mode, ks, g_ps_c, g_lvs_c, cmb);
-      } else if (pat >= 3 && (GWTF_K2_MASK & 8) && N % 128 == 0 && VAR == BW_MERGED) {
-        hipLaunchKernelGGL((bwd_kernel<MB, 2, VAR, 1, 0, true>), grid, block, 0, st, x_in, g_out, g_ld, pw_c, pb_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, g_stats, B, N, C, c, pat, eps, kk_steps, f, mode, ks, g_ps_c, g_lvs_c, cmb);
-      } else if (pat < 3 && (GWTF_K2_MASK & 4)) {
-        hipLaunchKernelGGL((bwd_kernel<MB, 2, VAR, 1, 1>), grid, block, 0, st, x_in, g_out, g_ld, pw_c, pb_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, g_stats, B, N, C, c, pat, eps, kk_steps, f, mode, ks, g_ps_c, g_lvs_c, cmb);
-      } else if (pat >= 3 && (GWTF_K2_MASK & 8)) {
-        hipLaunchKernelGGL((bwd_kernel<MB, 2, VAR, 1, 0>), grid, block, 0, st, x_in, g_out, g_ld, pw_c, pb_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, g_stats, B, N, C, c, pat, eps, kk_steps, f, mode, ks, g_ps_c, g_lvs_c, cmb);
-      } else {
-        hipLaunchKernelGGL((bwd_kernel<MB, 2, VAR, 1>), grid, block, 0, st, x_in, g_out, g_ld, pw_c, pb_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, g_stats, B, N, C, c, pat, eps, kk_steps, f, mode, ks, g_ps_c, g_lvs_c, cmb);
-      }
-      return (int)hipGetLastError();
+// ---- host side: plan, then launch ---------------------------------------------------------------------------------------------------
+// What a backward pass launches for a shape: the kernel variant <MB, NB, VAR = pass, MG, K2, FULL>, the tiles of one shape a workgroup
+// walks, and the grid.  MB == 0: refused (width beyond the kernels, or a grid that does not fit an int).
+struct BwdPlan { int MB, NB, MG, K2, FULL, tpw, grid_x, grid_y; };
+
+int bwd_nb(int B, int N) { return (long)B * N >= 2048L * 32 ? 2 : 1; }      // 128-point tiles from 64 Ki points up, 64 below
+// workgroups over the points: every shape's ceil(N / pts) tiles, tpw consecutive ones per workgroup
+long bwd_wgs(int B, int N, int pts, int tpw = 1) { return B * (((N + (long)pts - 1) / pts + tpw - 1) / tpw); }
+// the grid of the direct and merged passes = the partials one pass leaves in the dW1 workspace
+long bwd_grid(int B, int N) { return bwd_wgs(B, N, 64 * bwd_nb(B, N)); }
+bool fits_int(long v) { return v <= 0x7fffffffL; }      // a grid beyond an int is refused everywhere: plan, workspace size, reduction
+
+BwdPlan bwd_plan(int pass, int f, int B, int N, int K, int pat, int tune) {
+  const int nb = bwd_nb(B, N);
+  BwdPlan p = {gwtf_padded_width(f) / 16, nb, -1, -1, 0, 1, 0, K};
+  long grid = bwd_grid(B, N);
+  // forward-sized pass on a grid that fills the GPU: the forward kernel's tile (256 points per workgroup).
+  // GWTF_TUNE_SMALL_LIGHT_TILE: per-call diagnostic (tools/diag/light_tile_check.py)
+  const bool large_light = pass == BW_LIGHT && p.MB <= 3 && nb == 2 && (long)B * N * K >= 256L * 1024 && !(tune & GWTF_TUNE_SMALL_LIGHT_TILE);
+  if (gwtf_abs_form(f) && pass != BW_DIRECT) {
+    // the train pipeline's two passes at the abs-form widths (f = 33..40): the forward recompute as one basic block (MG = 1), and
+    // from 128-point tiles up the kernels compiled per warp pattern (K2)
+    p.MG = 1;
+    if (large_light) {
+      // as many of a shape's tiles per workgroup as still leave one full round of 512 resident workgroups
+      const int tps = (N + 255) / 256;
+      p.NB = 4;
+      p.tpw = (tune & GWTF_TUNE_SINGLE_TILE) ? 1 : (int)std::max(1L, std::min((long)tps, (long)B * tps * K / 512));
+      grid = bwd_wgs(B, N, 256, p.tpw);
     }
+    if (p.NB > 1) p.K2 = pat < 3 ? 1 : 0;
+    p.FULL = pass == BW_MERGED && p.NB == 2 && N % 128 == 0;
+  } else if (large_light) {
+    p.NB = 4;
+    grid = bwd_wgs(B, N, 256);
   }
-  if constexpr (VAR == BW_LIGHT && MB <= 3) {   // forward-sized pass: the forward kernel's tile (256 points per workgroup) where it fills the GPU
-    const bool small_tile = (ks.tune & GWTF_TUNE_SMALL_LIGHT_TILE) != 0;      // per-call diagnostic (tools/diag/light_tile_check.py)
-    if (nb == 2 && (long)B * N * K >= 256L * 1024 && !small_tile) {
-      const dim3 grid4((unsigned)(B * ((N + 255) / 256)), (unsigned)K);
-      hipLaunchKernelGGL((bwd_kernel<MB, 4, VAR>), grid4, block, 0, st, x_in, g_out, g_ld, pw_c, pb_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, g_stats, B, N, C, c, pat, eps, kk_steps, f, mode, ks, g_ps_c, g_lvs_c, cmb);
-      return (int)hipGetLastError();
-    }
+  if (p.MB < 1 || p.MB > 6 || !fits_int(grid)) return BwdPlan{};      // f > 96: the backward working set (forward + backward records) exceeds the LDS
+  p.grid_x = (int)grid;
+  return p;
+}
+
+// The one kernel call.  Stand-ins: a pass's kernels never dereference the operands the pass does not touch (GwtfBwdArgs says which;
+// VAR is a compile-time constant), so those slots carry no meaning.  They are filled with a live buffer of the same pass -- g_film in
+// the light pass (and its forward record for the backward record), g_sd0 in the merged pass -- not with the record's fields: the
+// kernels receive what they always have, and never a buffer another pass owns.
+template <int MB, int NB, int VAR, int MG = -1, int K2 = -1, bool FULL = false>
+int launch_plan(const BwdPlan& p, GwtfBwdArgs a) {
+  a.g_stats = VAR == BW_MERGED ? a.g_stats : nullptr;
+  if (VAR == BW_LIGHT) {
+    a.pb_c = a.pw_c;
+    a.g_in = a.dw1_ws = a.g_sd0 = a.g_film;
+  } else if (VAR == BW_MERGED) {
+    a.g_film = a.g_bias = a.g_sd0;
   }
-#define GWTF_B(NB_) hipLaunchKernelGGL((bwd_kernel<MB, NB_, VAR>), grid, block, 0, st, x_in, g_out, g_ld, pw_c, pb_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, g_stats, B, N, C, c, pat, eps, kk_steps, f, mode, ks, g_ps_c, g_lvs_c, cmb)
-  if (nb == 1) GWTF_B(1); else GWTF_B(2);
-#undef GWTF_B
+  a.ks.tpw = p.tpw;
+  hipLaunchKernelGGL((bwd_kernel<MB, NB, VAR, MG, K2, FULL>), dim3((unsigned)p.grid_x, (unsigned)p.grid_y), dim3(256), 0,
+                     (hipStream_t)a.stream, a.x_in, a.g_out, a.g_ld, a.pw_c, a.pb_c, a.film, a.g_in, a.dw1_ws, a.g_film, a.g_sd0,
+                     a.g_bias, a.g_stats, a.B, a.N, a.C, a.c, (a.pattern0 + a.c) % 6, a.eps, (a.f + 3) / 4, a.f, a.mode, a.ks,
+                     a.g_ps_c, a.g_lvs_c, a.cmb);
   return (int)hipGetLastError();
 }
+
+// The instantiation set: per width and pass the 64- and 128-point tiles; the light pass's 256-point tile up to MB = 3; at MB = 3 the
+// MG = 1 kernels of the light and merged passes -- one 64-point kernel, per warp-pattern class (K2) the 128-point one, the light
+// pass's 256-point one and the merged pass's full-tile one.  Nothing else is compiled (f = 37-sized kernels are the build's longest).
+template <int MB, int VAR>
+int launch_bwd(const BwdPlan& p, const GwtfBwdArgs& a) {
+  if constexpr (MB == 3 && VAR != BW_DIRECT) {
+    if (p.MG == 1) {
+      const bool one_warped = p.K2 == 1;      // bwd_plan: K2 is 1 or 0 on every arm that asks (NB > 1)
+      if constexpr (VAR == BW_LIGHT) {
+        if (p.NB == 4) return one_warped ? launch_plan<MB, 4, VAR, 1, 1>(p, a) : launch_plan<MB, 4, VAR, 1, 0>(p, a);
+      }
+      if (p.NB == 1) return launch_plan<MB, 1, VAR, 1>(p, a);
+      if constexpr (VAR == BW_MERGED) {
+        if (p.FULL) return one_warped ? launch_plan<MB, 2, VAR, 1, 1, true>(p, a) : launch_plan<MB, 2, VAR, 1, 0, true>(p, a);
+      }
+      return one_warped ? launch_plan<MB, 2, VAR, 1, 1>(p, a) : launch_plan<MB, 2, VAR, 1, 0>(p, a);
+    }
+  }
+  if constexpr (VAR == BW_LIGHT && MB <= 3) {
+    if (p.NB == 4) return launch_plan<MB, 4, VAR>(p, a);
+  }
+  return p.NB == 1 ? launch_plan<MB, 1, VAR>(p, a) : launch_plan<MB, 2, VAR>(p, a);
+}
+
+template <int MB>
+int launch_pass(int pass, const BwdPlan& p, const GwtfBwdArgs& a) {
+  switch (pass) {
+    case BW_DIRECT: return launch_bwd<MB, BW_DIRECT>(p, a);
+    case BW_LIGHT: return launch_bwd<MB, BW_LIGHT>(p, a);
+    default: return launch_bwd<MB, BW_MERGED>(p, a);
+  }
+}
+
+bool bwd_pass_ok(int pass) { return pass == BW_DIRECT || pass == BW_LIGHT || pass == BW_MERGED; }
 
 }  // namespace
 
@@ -713,37 +758,29 @@ extern "C" int gwtf_pack_folded(const float* W1p, const float* W0f, const float*
   return (int)hipGetLastError();
 }
 
-static int bwd_points_per_wg(int B, int N) { return (long)B * N >= 2048L * 32 ? 128 : 64; }
-static int bwd_grid(int B, int N) {
-  const int pts = bwd_points_per_wg(B, N);
-  return B * ((N + pts - 1) / pts);
+extern "C" int gwtf_bwd_plan(int pass, int f, int B, int N, int K, int pattern, int tune, int* out8) {
+  if (!out8 || !bwd_pass_ok(pass) || f <= 0 || f > GWTF_MAX_FP_TRAIN || B <= 0 || N <= 0 || K <= 0 || K > GWTF_MAX_COMPONENTS ||
+      pattern < 0 || pattern > 5)
+    return GWTF_E_BADARG;
+  const BwdPlan p = bwd_plan(pass, f, B, N, K, pattern, tune);
+  if (!p.MB) return GWTF_E_BADARG;
+  const int out[8] = {p.MB, p.NB, p.MG, p.K2, p.FULL, p.tpw, p.grid_x, p.grid_y};
+  std::copy(out, out + 8, out8);
+  return 0;
 }
 
-static int bwd_dispatch(int var, const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
-                        const float* packed_b_c, const float* film, float* g_in, float* dw1_ws, float* g_film, float* g_sd0,
-                        float* g_bias, const float* g_stats, int c, int B, int N, int C, int f, int pat, float eps, int mode,
-                        int K, const GwtfKS& ks, const float* g_ps_c, const float* g_lvs_c, const GwtfCombine& cmb, void* stream) {
-  const int kk_steps = (f + 3) / 4;
-  const int nb = bwd_points_per_wg(B, N) / 64;
-  hipStream_t st = (hipStream_t)stream;
-#define GWTF_A x_in, g_out, g_ld, packed_w_c, packed_b_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, g_stats, B, N, C, c, pat, eps, kk_steps, f, mode, K, ks, g_ps_c, g_lvs_c, cmb, st
-#define GWTF_V(MB_)                                                                                     \
-  switch (var) {                                                                                        \
-    case BW_DIRECT: return launch_bwd<MB_, BW_DIRECT>(nb, GWTF_A);                                      \
-    case BW_LIGHT: return launch_bwd<MB_, BW_LIGHT>(nb, GWTF_A);                                        \
-    default: return launch_bwd<MB_, BW_MERGED>(nb, GWTF_A);                                             \
+int gwtf_internal_backward_k(int pass, const GwtfBwdArgs& a) {
+  if (!bwd_pass_ok(pass)) return GWTF_E_BADARG;
+  const BwdPlan p = bwd_plan(pass, a.f, a.B, a.N, a.K, (a.pattern0 + a.c) % 6, a.ks.tune);
+  if (!p.MB) return GWTF_E_BADARG;
+  switch (p.MB) {
+    case 1: return launch_pass<1>(pass, p, a);
+    case 2: return launch_pass<2>(pass, p, a);
+    case 3: return launch_pass<3>(pass, p, a);
+    case 4: return launch_pass<4>(pass, p, a);
+    case 5: return launch_pass<5>(pass, p, a);
+    default: return launch_pass<6>(pass, p, a);
   }
-  switch (gwtf_padded_width(f) / 16) {
-    case 1: GWTF_V(1)
-    case 2: GWTF_V(2)
-    case 3: GWTF_V(3)
-    case 4: GWTF_V(4)
-    case 5: GWTF_V(5)
-    case 6: GWTF_V(6)
-    default: return GWTF_E_BADARG;       // f > 96: the backward working set (forward + backward records) exceeds the LDS
-  }
-#undef GWTF_A
-#undef GWTF_V
 }
 
 extern "C" int gwtf_coupling_backward_lists(const float* x_in, const float* g_out, const float* g_ld, const float* g_ps_c,
@@ -755,31 +792,14 @@ extern "C" int gwtf_coupling_backward_lists(const float* x_in, const float* g_ou
       !g_bias || B <= 0 || N <= 0 || C <= 0 || c < 0 || c >= C || f <= 0 || f > GWTF_MAX_FP_TRAIN || pattern0 < 0 || pattern0 > 5 ||
       (mode != GWTF_MODE_DIRECT && mode != GWTF_MODE_INVERSE))
     return GWTF_E_BADARG;
-  GwtfKS ks = {};
-  ks.Cper = ks.Ctot = C;
-  return bwd_dispatch(BW_DIRECT, x_in, g_out, g_ld, packed_w_c, packed_b_c, film, g_in, dw1_ws, g_film, g_sd0, g_bias, nullptr, c,
-                      B, N, C, f, (pattern0 + c) % 6, eps, mode, 1, ks, g_ps_c, g_lvs_c, GwtfCombine{}, stream);
-}
-
-// The train pipeline's two passes (BW_LIGHT / BW_MERGED above; gwtf_train.hip): component k adds k * stride (GwtfKS) to every base
-// pointer.  light: only g_film and g_bias are written; merged: g_in, the dW1 partials and g_sd0, with the statistics path's upstream
-// g_stats [K][2][2][FP] added to dacc.
-int gwtf_internal_light_backward_k(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
-                                   const float* film, float* g_film, float* g_bias, int c, int K, int B, int N, int f,
-                                   int pattern0, float eps, int mode, const GwtfKS& ks, const float* g_ps_c,
-                                   const float* g_lvs_c, const GwtfCombine& cmb, void* stream) {
-  return bwd_dispatch(BW_LIGHT, x_in, g_out, g_ld, packed_w_c, packed_w_c /*unused*/, film, g_film /*unused*/, g_film /*unused*/,
-                      g_film, g_film /*unused*/, g_bias, nullptr, c, B, N, ks.Ctot, f, (pattern0 + c) % 6, eps, mode, K, ks, g_ps_c,
-                      g_lvs_c, cmb, stream);
-}
-int gwtf_internal_merged_backward_k(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
-                                    const float* packed_b_c, const float* film, const float* g_stats, float* g_in, float* dw1_ws,
-                                    float* g_sd0, int c, int K, int B, int N, int f, int pattern0, float eps, int mode,
-                                    const GwtfKS& ks, const float* g_ps_c, const float* g_lvs_c, const GwtfCombine& cmb,
-                                    void* stream) {
-  return bwd_dispatch(BW_MERGED, x_in, g_out, g_ld, packed_w_c, packed_b_c, film, g_in, dw1_ws, g_sd0 /*unused*/, g_sd0,
-                      g_sd0 /*unused*/, g_stats, c, B, N, ks.Ctot, f, (pattern0 + c) % 6, eps, mode, K, ks, g_ps_c, g_lvs_c, cmb,
-                      stream);
+  GwtfBwdArgs a = {};
+  a.x_in = x_in; a.g_out = g_out; a.g_ld = g_ld; a.pw_c = packed_w_c; a.pb_c = packed_b_c; a.film = film;
+  a.g_in = g_in; a.dw1_ws = dw1_ws; a.g_film = g_film; a.g_sd0 = g_sd0; a.g_bias = g_bias;
+  a.g_ps_c = g_ps_c; a.g_lvs_c = g_lvs_c;
+  a.B = B; a.N = N; a.C = C; a.c = c; a.f = f; a.pattern0 = pattern0; a.mode = mode; a.K = 1; a.eps = eps;
+  a.ks.Cper = a.ks.Ctot = C;
+  a.stream = stream;
+  return gwtf_internal_backward_k(BW_DIRECT, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -804,7 +824,7 @@ __global__ __launch_bounds__(256) void dw1_reduce_kernel(const float* __restrict
 }
 }  // namespace
 
-extern "C" int gwtf_dw1_partials(int B, int N) { return (B > 0 && N > 0) ? bwd_grid(B, N) : 0; }
+extern "C" int gwtf_dw1_partials(int B, int N) { return (B > 0 && N > 0 && fits_int(bwd_grid(B, N))) ? (int)bwd_grid(B, N) : 0; }
 
 extern "C" size_t gwtf_dw1_workspace_floats(int f, int B, int N) {
   return (size_t)gwtf_dw1_partials(B, N) * gwtf_dw1::rec_floats(f);      // [2][f][RP] partials (gwtf_dw1.h)
@@ -819,8 +839,9 @@ int gwtf_internal_dw1_reduce_k(float* workspace, int passes, float* dW1, size_t 
                                size_t ws_sk, size_t out_sk, void* stream) {
   if (!workspace || !dW1 || passes < 1 || f <= 0 || f > GWTF_MAX_FP_TRAIN || B <= 0 || N <= 0 || K <= 0 || branch_stride < (size_t)f * f)
     return GWTF_E_BADARG;
+  if (!fits_int(passes * bwd_grid(B, N))) return GWTF_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
-  const int FP = gwtf_padded_width(f), rec = gwtf_dw1::rec_floats(f), n_partials = passes * bwd_grid(B, N);
+  const int FP = gwtf_padded_width(f), rec = gwtf_dw1::rec_floats(f), n_partials = passes * (int)bwd_grid(B, N);
   float* mid = workspace + (size_t)n_partials * rec;
   hipLaunchKernelGGL(dw1_fold_kernel, dim3((rec + 255) / 256, kDw1Stage, K), dim3(256), 0, st, workspace, n_partials, mid, rec, ws_sk);
   hipLaunchKernelGGL(dw1_reduce_kernel, dim3((gwtf_dw1::rec_floats(f) + 63) / 64, K), dim3(256), 0, st, mid, dW1, FP, f, branch_stride, ws_sk, out_sk);

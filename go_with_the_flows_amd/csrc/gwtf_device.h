@@ -397,15 +397,33 @@ int gwtf_internal_stats_k(const float* p, const float* packed_w_c, float* ystats
 // ... and coupling c alone of the K stacks of `a` in one launch: component k continues logdet_in + k * out_stride_k (null: starts at
 // zero) and accumulates the next coupling's moments into moments_out + k * moments_stride_k (null: none).
 int gwtf_internal_apply_k(const GwtfStackArgs& a, int c, const float* logdet_in, float* moments_out, size_t moments_stride_k);
-// gwtf_bwd.hip
-int gwtf_internal_light_backward_k(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
-                                   const float* film, float* g_film, float* g_bias, int c, int K, int B, int N, int f,
-                                   int pattern0, float eps, int mode, const GwtfKS& ks, const float* g_ps_c,
-                                   const float* g_lvs_c, const GwtfCombine& cmb, void* stream);
-int gwtf_internal_merged_backward_k(const float* x_in, const float* g_out, const float* g_ld, const float* packed_w_c,
-                                    const float* packed_b_c, const float* film, const float* g_stats, float* g_in, float* dw1_ws,
-                                    float* g_sd0, int c, int K, int B, int N, int f, int pattern0, float eps, int mode,
-                                    const GwtfKS& ks, const float* g_ps_c, const float* g_lvs_c, const GwtfCombine& cmb,
-                                    void* stream);
+// gwtf_bwd.hip: everything one backward launch takes.  Component k of a launch adds k * stride (ks) to every base pointer.
+struct GwtfBwdArgs {
+  const float* x_in;      // the coupling's input saved by the forward
+  const float* g_out;     // dL/d out: the previous backward level's RAW gradient when cmb.gm is set
+  const float* g_ld;      // dL/d logdet
+  const float* pw_c;      // this coupling's forward record (packed_w)
+  const float* pb_c;      // ... and backward record (packed_b); the light pass leaves it alone
+  const float* film;      // FiLM records [B][Ctot][gwtf_film_out_floats]
+  float* g_in;            // written by the direct and merged passes; the light pass leaves it alone
+  float* dw1_ws;          // per-workgroup dW1 partials (gwtf_dw1_workspace_floats): direct and merged passes; light leaves it alone
+  float* g_film;          // += {dc, du0, du1}: direct and light passes; merged leaves it alone
+  float* g_sd0;           // += sd0 sums: direct and merged passes; light leaves it alone
+  float* g_bias;          // += sd2 bias sums: direct and light passes; merged leaves it alone
+  const float* g_stats;   // the statistics path's upstream [K][2][2][FP], added to dacc: merged pass only; null otherwise
+  const float* g_ps_c;    // dL/d ps[c], dL/d logvars[c]: gradients entering through the coupling's own list slots;
+  const float* g_lvs_c;   //   either may be null
+  int B, N;
+  int C;                  // couplings per FiLM row as the caller counts them (the kernels index the FiLM arrays by ks.Ctot)
+  int c, f, pattern0, mode;
+  int K;                  // components = grid.y
+  float eps;
+  GwtfKS ks;              // per-component strides + the call's tuning word
+  GwtfCombine cmb;        // the previous level's gradient combine (light and merged passes; gm null: none)
+  void* stream;
+};
+// One backward pass (GWTF_BWD_PASS_*) of coupling a.c: direct = the coupling's whole backward; light / merged = the train pipeline's
+// two passes (light: only g_film and g_bias are written; merged: g_in, the dW1 partials and g_sd0).
+int gwtf_internal_backward_k(int pass, const GwtfBwdArgs& a);
 int gwtf_internal_dw1_reduce_k(float* workspace, int passes, float* dW1, size_t branch_stride, int f, int B, int N, int K,
                                size_t ws_sk, size_t out_sk, void* stream);

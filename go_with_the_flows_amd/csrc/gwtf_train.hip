@@ -727,11 +727,7 @@ extern "C" int gwtf_mtrain_phase(const GwtfTrainCtx* t, int phase, int step) {
   float* g_bias = t->g_bias + (size_t)c * K * d.GB;
   float* g_stats = t->g_stats + (size_t)c * K * d.GST;
   float* g_mom = t->g_mom + (size_t)c * K * d.GM;
-  const float* pw_c = t->packed_w + (size_t)c * d.PW;
-  const float* pb_c = t->packed_b + (size_t)c * d.PB;
   float* g_raw_c = t->g_raw + (size_t)c * d.RC;
-  const float* g_ps_c = t->g_ps ? t->g_ps + (size_t)c * d.XS : nullptr;
-  const float* g_lvs_c = t->g_lvs ? t->g_lvs + (size_t)c * d.XS : nullptr;
   const GwtfRaw R(f, G);
   const int rec = gwtf_dw1::rec_floats(f), n_partials = gwtf_dw1_partials(B, N);
   const size_t scratch = gwtf_dw1_reduce_scratch_floats(f);
@@ -742,17 +738,25 @@ extern "C" int gwtf_mtrain_phase(const GwtfTrainCtx* t, int phase, int step) {
     cmb.gm = t->g_mom + (size_t)c_prev * K * d.GM;
     cmb.gm_sk = d.GM;
   }
+  // this step's backward launches: one record, read by the light (BWD_A) and the merged (BWD_B) pass
+  GwtfBwdArgs a = {};
+  a.x_in = x_in; a.g_out = cur; a.g_ld = t->g_ld; a.film = t->film_rec;
+  a.pw_c = t->packed_w + (size_t)c * d.PW;
+  a.pb_c = t->packed_b + (size_t)c * d.PB;
+  a.g_in = nxt; a.dw1_ws = t->dw1_ws; a.g_film = t->g_film; a.g_sd0 = g_sd0; a.g_bias = g_bias; a.g_stats = g_stats;
+  a.g_ps_c = t->g_ps ? t->g_ps + (size_t)c * d.XS : nullptr;
+  a.g_lvs_c = t->g_lvs ? t->g_lvs + (size_t)c * d.XS : nullptr;
+  a.B = B; a.N = N; a.C = ks.Ctot; a.c = c; a.f = f; a.pattern0 = t->pattern0; a.mode = t->mode; a.K = K; a.eps = t->eps;
+  a.ks = ks; a.cmb = cmb; a.stream = t->stream;
   if (phase == GWTF_PHASE_BWD_A) {
-    int rc = gwtf_internal_light_backward_k(x_in, cur, t->g_ld, pw_c, t->film_rec, t->g_film, g_bias, c, K, B, N, f, t->pattern0,
-                                            t->eps, t->mode, ks, g_ps_c, g_lvs_c, cmb, t->stream);
+    int rc = gwtf_internal_backward_k(GWTF_BWD_PASS_LIGHT, a);
     if (rc) return rc;
     hipLaunchKernelGGL(fold1_bwd_kernel, dim3(2, FP / 16, K), dim3(kF1Slices * 16), 0, st, t->raw + (size_t)c * d.RC, ys.p,
                        t->n_total, t->film_raw, t->g_film, g_bias, t->g_film_raw, g_raw_c, g_stats, c, B, C, f, G, FP, ks, ys.nr);
     return (int)hipGetLastError();
   }
   if (phase == GWTF_PHASE_BWD_B) {
-    int rc = gwtf_internal_merged_backward_k(x_in, cur, t->g_ld, pw_c, pb_c, t->film_rec, g_stats, nxt, t->dw1_ws, g_sd0, c, K, B,
-                                             N, f, t->pattern0, t->eps, t->mode, ks, g_ps_c, g_lvs_c, cmb, t->stream);
+    int rc = gwtf_internal_backward_k(GWTF_BWD_PASS_MERGED, a);
     if (rc) return rc;
     // sd0 fold's backward | stage 1 of this level's dW1 reduction | stage 2 of the previous level's: one launch
     const float* mid_prev = step > 0 ? t->dw1_ws + (size_t)n_partials * rec + (size_t)(c_prev & 1) * scratch : nullptr;

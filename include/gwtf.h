@@ -156,6 +156,17 @@ int gwtf_latent_loss_rows_backward(const float* g_out4, const float* z, const fl
  * launch, out[1] = its workgroups, out[2] = points per wavefront of the tail launch (0: none), out[3] = its workgroups.
  * The choice minimises resident rounds x the cost of a round of that tile (calibrated, csrc/gwtf_stack.hip tile_cost). */
 int gwtf_stack_plan(const int* segments, int K, int B, int N, int f, int tune, int* out4);
+/* The passes of the coupling backward, by the kernels' own values. */
+#define GWTF_BWD_PASS_DIRECT 0   /* the coupling's whole backward (gwtf_coupling_backward_lists) */
+#define GWTF_BWD_PASS_LIGHT 2    /* train pipeline, phase BWD_A: FiLM-record and bias sums only */
+#define GWTF_BWD_PASS_MERGED 3   /* train pipeline, phase BWD_B: g_in, dW1 partials, sd0 sums */
+/* Launch plan of one backward pass (GWTF_BWD_PASS_*) of a coupling (what csrc/gwtf_bwd.hip bwd_plan decides; diagnostic + tests,
+ * launches nothing): out8 = {MB, NB, MG, K2, FULL, tpw, grid_x, grid_y} -- the kernel variant (MB = padded width / 16, NB = 64-point
+ * blocks per workgroup tile, MG / K2 / FULL as in the kernel's template), the tiles of one shape a workgroup walks, and the grid.
+ * The direct and merged passes' grid_x is gwtf_dw1_partials(B, N).  pattern = (pattern0 + c) % 6.
+ * GWTF_E_BADARG: NULL out8, unknown pass, f outside 1..96, B, N or K <= 0, K > 64, pattern outside 0..5, a grid beyond an int
+ * (gwtf_dw1_partials and gwtf_dw1_workspace_floats return 0 for such a shape, gwtf_dw1_reduce refuses it). */
+int gwtf_bwd_plan(int pass, int f, int B, int N, int K, int pattern, int tune, int* out8);
 
 /* ---- backward (both directions, BatchNorm as a fixed affine) --------------------------------------------------
  * Autograd of CondRealNVPFlow3D.forward (reference flows.py:95-117 as differentiated by loss.backward(),
