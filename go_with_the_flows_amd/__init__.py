@@ -11,6 +11,7 @@ from .prior import RealNVPFlow, RealNVPFlowCouple, GlobalRNVPDecoder, GaussianFl
 from .models import Local_Cond_RNVP_MC_Global_RNVP_VAE, Flow_Mixture_Model, Flow_Mixture_SVR_Model, Flow_Mixture_Loss, FlowMixtureNLL
 from .resnet import ResNet, BasicBlock, resnet18
 from .clouds import MeshStore, CloudTransform, DeviceCloudLoader, sample_clouds, make_state
+from .images import ImageStore, ImageTransform, DeviceSVRLoader, transform_images
 from ._lib import GwtfError
 
 __all__ = ['SharedDot', 'Swish', 'CondRealNVPFlow3D', 'CondRealNVPFlow3DTriple', 'LocalCondRNVPDecoder',
@@ -18,4 +19,5 @@ __all__ = ['SharedDot', 'Swish', 'CondRealNVPFlow3D', 'CondRealNVPFlow3DTriple',
            'PointNetCloudEncoder', 'FeatureEncoder', 'WeightsEncoder', 'RealNVPFlow', 'RealNVPFlowCouple',
            'GlobalRNVPDecoder', 'GaussianFlowNLL', 'GaussianEntropy', 'Local_Cond_RNVP_MC_Global_RNVP_VAE',
            'Flow_Mixture_Model', 'Flow_Mixture_SVR_Model', 'Flow_Mixture_Loss', 'FlowMixtureNLL', 'ResNet', 'BasicBlock',
-           'resnet18', 'MeshStore', 'CloudTransform', 'DeviceCloudLoader', 'sample_clouds', 'make_state']
+           'resnet18', 'MeshStore', 'CloudTransform', 'DeviceCloudLoader', 'sample_clouds', 'make_state',
+           'ImageStore', 'ImageTransform', 'DeviceSVRLoader', 'transform_images']

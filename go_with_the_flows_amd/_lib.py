@@ -110,6 +110,7 @@ _SIGNATURES = {
     'gwtf_route_tiles': (ctypes.c_int, [ctypes.c_int] * 3),
     'gwtf_mixture_route': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_stack_forward_routed': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_transform_images': (ctypes.c_int, [ctypes.c_void_p]),
 }
 
 PHASE_FWD_INIT, PHASE_FWD_A, PHASE_FWD_B, PHASE_BWD_A, PHASE_BWD_B, PHASE_BWD_C = range(6)
@@ -182,6 +183,15 @@ class RoutedStackArgs(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_void_p) for n in ('zp', 'weights', 'film', 'tile_comp', 'perm', 'out', 'logdet')] +
                 [(n, ctypes.c_int) for n in ('K', 'S', 'n', 'P', 'C', 'f', 'pattern0', 'tune')] +
                 [('eps', ctypes.c_float), ('stream', ctypes.c_void_p)])
+
+
+class ImageArgs(ctypes.Structure):
+    """GwtfImageArgs of include/gwtf.h (one batch of transformed images): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('images', 'rows', 'xs', 'xf', 'ys', 'yf', 'noise', 'state', 'out')] +
+                [(n, ctypes.c_int) for n in ('B', 'n_images', 'C', 'H', 'W', 'H_r', 'W_r', 'pad_y', 'pad_x', 'resize', 'grayscale',
+                                             'normalize', 'add_noise', 'remove_alpha')] +
+                [('gray', ctypes.c_float * 3), ('mean', ctypes.c_float * 5), ('stdev', ctypes.c_float * 5),
+                 ('noise_scale', ctypes.c_float), ('stream', ctypes.c_void_p)])
 
 
 EXPORTS = tuple(_SIGNATURES)

@@ -247,6 +247,23 @@ def sample_clouds(store, rows, cloud_size, return_eval_cloud=True, transform=Non
 _IDENTITY = CloudTransform()
 
 
+def epoch_plan(n, shuffle, seed, epoch, rank=0, world_size=1):
+    """One rank's item indices of one epoch over n items, in order (host, int64 numpy): torch.randperm under a generator seeded
+    seed + epoch, then the padding and stride of torch.utils.data.DistributedSampler (drop_last=False).  The loaders of this
+    module and of images.py share it."""
+    if shuffle:
+        g = torch.Generator()
+        g.manual_seed(seed + epoch)
+        idx = torch.randperm(n, generator=g).tolist()
+    else:
+        idx = list(range(n))
+    total = -(-n // world_size) * world_size
+    pad = total - len(idx)
+    if pad > 0:
+        idx += (idx * -(-pad // len(idx)))[:pad]
+    return np.asarray(idx[rank:total:world_size], np.int64)
+
+
 class DeviceCloudLoader:
     """Stands where DataLoader(ShapeNetCoreDataset(...), batch_size, shuffle=True, drop_last=True) stood (train_ae.py:85-116): an
     iterable of device batches.  The epoch's order is a host permutation from (seed, epoch) -- torch.randperm under a generator
@@ -274,19 +291,8 @@ class DeviceCloudLoader:
 
     def index_plan(self, epoch=None):
         """This rank's shape indices for one epoch, in order (host, int64 numpy); batches are consecutive slices of it."""
-        epoch = self.epoch if epoch is None else int(epoch)
-        n = len(self.store)
-        if self.shuffle:
-            g = torch.Generator()
-            g.manual_seed(self.seed + epoch)
-            idx = torch.randperm(n, generator=g).tolist()
-        else:
-            idx = list(range(n))
-        total = self.num_samples * self.world_size
-        pad = total - len(idx)
-        if pad > 0:
-            idx += (idx * -(-pad // len(idx)))[:pad]
-        return np.asarray(idx[self.rank:total:self.world_size], np.int64)
+        return epoch_plan(len(self.store), self.shuffle, self.seed, self.epoch if epoch is None else int(epoch), self.rank,
+                          self.world_size)
 
     def __iter__(self):
         dev = self.store.device

@@ -687,6 +687,52 @@ int gwtf_route_tiles(int n, int K, int P);
 int gwtf_mixture_route(const GwtfRouteArgs* args);
 int gwtf_stack_forward_routed(const GwtfRoutedStackArgs* args);
 
+/* Image batches transformed on the device (csrc/gwtf_images.hip; added without a version change, no existing record or signature
+ * moved): what ShapeNetAllDataset.__getitem__ (lib/datasets/datasets.py:173-222) and ComposeImageTransformation
+ * (lib/datasets/image_transformations.py:7-95) do per item on the host, for B images of a store of raw uint8 renderings
+ * [n_images][C][H][W], C in {3, 4}, in ONE launch.  Stage order and arithmetic, all float32 and uncontracted:
+ *   ToNumpy     v_c = (float)byte / 255.f, correctly rounded (the bits of np.float32(byte / 255.) for all 256 bytes); then
+ *               v_0 = v_2 * v_0, v_1 = v_2 * v_1 (channel 2, not alpha: image_transformations.py:13)
+ *   Resize      cv2's INTER_LINEAR from per-axis tables the HOST computes in float64 and rounds: column x of the resized image reads
+ *               source columns xs[x] and min(xs[x] + 1, W - 1) with weights 1.f - xf[x] and xf[x], rows likewise from ys / yf;
+ *               r = S[s0] * a0 + S[s1] * a1 along x first, then out = r0 * b0 + r1 * b1 along y
+ *   Pad         pad_y zero rows above and below, pad_x zero columns left and right (before grayscale and normalisation)
+ *   Grayscale   a new channel 0 = (gray[0] * v_0 + gray[1] * v_1) + gray[2] * v_2; the others move up by one
+ *   Normalize   (v_c - mean[c]) / stdev[c], correctly rounded, c the channel at this stage
+ *   Noise       min(max(v_c + n_c, 0), 1): n from `noise` ([B][C_stage][H_out][W_out], already scaled) or, when that is NULL,
+ *               noise_scale * z with z from Philox4x32-10, key (seed lo, seed hi), counter (y * W_out + x, b, call lo,
+ *               call hi | stream << 28): stream 4 Box-Muller normals from (word 0, word 1) -> channels 0, 1 and (word 2, word 3) ->
+ *               channels 2, 3; stream 5 (word 0, word 1) -> channel 4.  A second, one-thread launch then stores call + 1 into state[1]
+ *   RemoveAlpha keeps the first four channels
+ * C_stage = C + gray, C_out = remove_alpha ? min(C_stage, 4) : C_stage; H_out = H_r + 2 pad_y, W_out = W_r + 2 pad_x with
+ * (H_r, W_r) the resized size (the source's without resize).  A source channel no output channel needs is never loaded.
+ * rows[b] names the source image of output b (NULL: image b); an index outside [0, n_images) yields an all-NaN image and reads
+ * nothing.  Each thread stores four consecutive x of every channel as one 16-byte store; W_out % 4 columns take scalar stores. */
+typedef struct GwtfImageArgs {
+  const unsigned char* images;       /* [n_images][C][H][W] */
+  const int* rows;                   /* [B] or NULL */
+  const int* xs;                     /* [W_r], read when resize */
+  const float* xf;                   /* [W_r] */
+  const int* ys;                     /* [H_r] */
+  const float* yf;                   /* [H_r] */
+  const float* noise;                /* explicit noise or NULL */
+  unsigned long long* state;         /* {seed, call}; required when noise is on and `noise` is NULL */
+  float* out;                        /* [B][C_out][H_out][W_out] */
+  int B, n_images, C, H, W;
+  int H_r, W_r;
+  int pad_y, pad_x;
+  int resize, grayscale, normalize, add_noise, remove_alpha;
+  float gray[3];
+  float mean[5], stdev[5];           /* per channel at the normalisation stage */
+  float noise_scale;                 /* > 0 when Philox noise is drawn */
+  void* stream;
+} GwtfImageArgs;
+/* GWTF_E_BADARG without a launch: a NULL record or required pointer, B outside 1..65535, C outside {3, 4}, sizes < 1, negative
+ * padding, H_r / W_r other than H / W without resize, a stdev <= 0 with normalize, Philox noise without a state or with
+ * noise_scale <= 0.  GWTF_E_UNSUPPORTED: source rows too wide for the staging buffer (8 rows with
+ * resize, 4 without, of the channels read, W floats each, plus the column table with resize, beyond 64 KiB). */
+int gwtf_transform_images(const GwtfImageArgs* args);
+
 #ifdef __cplusplus
 }
 #endif
