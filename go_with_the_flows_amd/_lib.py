@@ -111,6 +111,9 @@ _SIGNATURES = {
     'gwtf_mixture_route': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_stack_forward_routed': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_transform_images': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_norm2d_partials': (ctypes.c_int, [ctypes.c_int] * 4),
+    'gwtf_norm2d_forward': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_norm2d_backward': (ctypes.c_int, [ctypes.c_void_p]),
 }
 
 PHASE_FWD_INIT, PHASE_FWD_A, PHASE_FWD_B, PHASE_BWD_A, PHASE_BWD_B, PHASE_BWD_C = range(6)
@@ -192,6 +195,14 @@ class ImageArgs(ctypes.Structure):
                                              'normalize', 'add_noise', 'remove_alpha')] +
                 [('gray', ctypes.c_float * 3), ('mean', ctypes.c_float * 5), ('stdev', ctypes.c_float * 5),
                  ('noise_scale', ctypes.c_float), ('stream', ctypes.c_void_p)])
+
+
+class Norm2dArgs(ctypes.Structure):
+    """GwtfNorm2dArgs of include/gwtf.h (one fused train-mode BatchNorm2d layer, either direction): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('x', 'residual', 'gamma', 'beta', 'running_mean', 'running_var', 'y', 'offsets', 'stats',
+                                                'partials', 'dy', 'dx', 'd_residual', 'dgamma', 'dbeta')] +
+                [(n, ctypes.c_int) for n in ('N', 'C', 'H', 'W', 'relu', 'pool')] +
+                [('eps', ctypes.c_float), ('momentum', ctypes.c_float), ('stream', ctypes.c_void_p)])
 
 
 EXPORTS = tuple(_SIGNATURES)

@@ -9,17 +9,21 @@ Two paths, the split the PointNet encoder had before its training kernels:
   csrc/gwtf_resnet.hip (implicit-GEMM convolutions on the fp32 matrix cores with every BatchNorm folded in, split-K with a
   fixed-order reduction at small batch, max-pool, the head in one launch);
 * train mode, or whenever a gradient must flow through the encoder: the plain torch modules (library convolutions, batch
-  statistics, autograd).  A HIP training path (convolution backward, BatchNorm2d batch statistics) is not built yet
-  (DESIGN section 8).
+  statistics, autograd).  With the class attribute ``ResNet.train_norm = 'hip'`` (default ``'library'``) a train-mode call keeps the
+  library convolutions but runs every BatchNorm2d with the ReLU, residual add and stem max-pool behind it through the fused
+  kernels of csrc/gwtf_norm2d.hip (norm2d.norm_act_2d), forward and backward; the head stays on the modules.  Convolution
+  backward in HIP and SyncBatchNorm are not built.
 ``forward_torch`` runs the module graph on any device and dtype (the CPU float64 evaluation the tests compare against).
 An eval-mode call that the kernels cannot take (CPU tensor, dtype other than float32, channels other than 4, images under
 32 x 32) raises GwtfError: there is no fallback.
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 from ._lib import GwtfError, _ptr, _stream, check
+from .norm2d import norm_act_2d
 
 
 def _conv3x3(in_planes, out_planes, stride=1):
@@ -51,7 +55,13 @@ class BasicBlock(nn.Module):
         return self.relu(y)
 
 
+def _conv(conv, x):
+    return F.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups)
+
+
 class ResNet(nn.Module):
+    train_norm = 'library'      # 'hip': train-mode BatchNorm2d (+ ReLU, residual, stem pool) on csrc/gwtf_norm2d.hip; not in state_dict
+
     def __init__(self, block, layers, num_classes=1000, zero_init_residual=False, groups=1, width_per_group=64,
                  replace_stride_with_dilation=None, norm_layer=None):
         super().__init__()
@@ -113,6 +123,20 @@ class ResNet(nn.Module):
     def forward_torch(self, x):
         x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        x = torch.flatten(self.avgpool(x), 1)
+        return self.relu(self.fc_bn(self.fc(x)))
+
+    def forward_train_hip(self, x):
+        """The train-mode module graph with library convolutions and the fused BatchNorm2d kernels; same parameters, buffers and
+        running-statistics updates as forward_torch in train mode."""
+        if not self._hip_ok:
+            raise GwtfError("train_norm='hip' covers resnet18 (BasicBlock x [2,2,2,2], BatchNorm2d) only")
+        x = norm_act_2d(_conv(self.conv1, x), self.bn1, pool=True)
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for blk in layer:
+                y = norm_act_2d(_conv(blk.conv1, x), blk.bn1)
+                r = x if blk.downsample is None else norm_act_2d(_conv(blk.downsample[0], x), blk.downsample[1], relu=False)
+                x = norm_act_2d(_conv(blk.conv2, y), blk.bn2, residual=r)
         x = torch.flatten(self.avgpool(x), 1)
         return self.relu(self.fc_bn(self.fc(x)))
 
@@ -217,10 +241,15 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         if self._needs_graph(x):
+            if self.train_norm not in ('library', 'hip'):
+                raise GwtfError(f"train_norm must be 'library' or 'hip', got {self.train_norm!r}")
+            if self.train_norm == 'hip' and not self._hip_ok:
+                raise GwtfError("train_norm='hip' covers resnet18 (BasicBlock x [2,2,2,2], BatchNorm2d) only")
             if not x.is_cuda:
                 raise GwtfError(f'images must live on a HIP device (got {x.device}); forward_torch evaluates the module '
                                 'graph anywhere')
-            return self.forward_torch(x)
+            # eval mode with autograd keeps the library graph: the fused kernels compute batch statistics
+            return self.forward_train_hip(x) if self.train_norm == 'hip' and self.training else self.forward_torch(x)
         return self.forward_hip(x)
 
 

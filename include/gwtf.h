@@ -25,6 +25,7 @@ extern "C" {
 #define GWTF_ABI_VERSION 11
 #define GWTF_E_BADARG 10001   /* shape / mode / width outside what the kernels support */
 #define GWTF_E_UNSUPPORTED 10002   /* a layer-width list no kernel instantiation was built for */
+#define GWTF_E_FEW_VALUES 10003   /* batch statistics over fewer than 2 values per channel */
 #define GWTF_MODE_DIRECT 0    /* sampling direction  base -> data (reference models.py:202) */
 #define GWTF_MODE_INVERSE 1   /* density direction   data -> base (reference models.py:197) */
 
@@ -732,6 +733,49 @@ typedef struct GwtfImageArgs {
  * noise_scale <= 0.  GWTF_E_UNSUPPORTED: source rows too wide for the staging buffer (8 rows with
  * resize, 4 without, of the channels read, W floats each, plus the column table with resize, beyond 64 KiB). */
 int gwtf_transform_images(const GwtfImageArgs* args);
+
+/* Train-mode BatchNorm2d fused with what follows it in the image encoder (csrc/gwtf_norm2d.hip; added without a version change, no
+ * existing record or signature moved).  Contiguous NCHW float32; batch statistics over N * H * W values per channel: biased variance
+ * for the normalisation, eps inside the square root, running_mean / running_var updated in place with `momentum` (the unbiased
+ * variance goes into running_var).  xhat = (x - mean) * rstd, and
+ *   relu = 0                    y = gamma * xhat + beta
+ *   relu = 1                    y = relu(gamma * xhat + beta + residual)     (residual may be NULL)
+ *   relu = 1, pool = 1          y = MaxPool2d(3, stride 2, padding 1) of relu(gamma * xhat + beta): y and offsets are
+ *                               [N][C][Ho][Wo], Ho = (H - 1) / 2 + 1; offsets holds 3 * dy + dx (0..8) of the first maximum of the
+ *                               window in row-major order, padding counting as -inf (torch's rule); no residual
+ * Forward: partial sums (float64, a (C, S) grid, S = gwtf_norm2d_partials), a finalising launch that adds them in a fixed order
+ * and writes stats = [3][C] {mean, rstd, mean - (float)mean} and the running statistics, the applying launch.  Backward, with
+ * dy' = dy * [y > 0] (relu; y the saved output), = dy (no relu), or gathered from the pooled gradient through `offsets` with y
+ * recomputed from x by the forward's arithmetic (pool): dgamma = sum dy' * xhat, dbeta = sum dy',
+ * dx = gamma * rstd * (dy' - mean(dy') - xhat * mean(dy' * xhat)), d_residual = dy' when asked for.  No atomics: two calls give
+ * the same bits.  Any H * W >= 1 and any alignment are taken (16-byte accesses when planes and addresses allow, else 4-byte). */
+typedef struct GwtfNorm2dArgs {
+  const float* x;                    /* [N][C][H][W] */
+  const float* residual;             /* as x, or NULL */
+  const float* gamma;                /* [C] */
+  const float* beta;                 /* [C]; the backward reads it with pool only */
+  float* running_mean;               /* [C], forward; NULL: not updated */
+  float* running_var;
+  float* y;                          /* forward: the output; backward: the saved output (read when relu and not pool) */
+  unsigned char* offsets;            /* [N][C][Ho][Wo] with pool */
+  float* stats;                      /* [3][C]: written by the forward, read by the backward */
+  double* partials;                  /* [C][S][2] */
+  const float* dy;                   /* backward: the gradient of y */
+  float* dx;
+  float* d_residual;                 /* or NULL */
+  float* dgamma;                     /* [C] */
+  float* dbeta;                      /* [C] */
+  int N, C, H, W;
+  int relu, pool;
+  float eps, momentum;
+  void* stream;
+} GwtfNorm2dArgs;
+/* All three validate on the host before any launch.  GWTF_E_BADARG: a NULL record or required pointer, a size < 1, N > 65535,
+ * N * H * W or C * H * W near 2^31, pool without relu or with a residual, eps < 0, momentum outside [0, 1].  GWTF_E_FEW_VALUES:
+ * N * H * W < 2 (torch refuses the same).  gwtf_norm2d_partials returns S (1..64), or 0 for sizes the launches reject. */
+int gwtf_norm2d_partials(int N, int C, int H, int W);
+int gwtf_norm2d_forward(const GwtfNorm2dArgs* args);
+int gwtf_norm2d_backward(const GwtfNorm2dArgs* args);
 
 #ifdef __cplusplus
 }

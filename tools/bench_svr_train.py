@@ -16,8 +16,15 @@ initial state with the same injected reparameterisation noise: its four loss ter
                                     [--out profiles/r21_svr_train.jsonl]
     python tools/bench_svr_train.py --profile-steps 20 --batches 128        # graphed variant only, for rocprofv3 --kernel-trace
     python tools/bench_svr_train.py --profile-encoder 20 --batches 128      # the image encoder alone (library forward + backward)
+    python tools/bench_svr_train.py --encoder-norm library,hip --variants graphed --out profiles/r23_svr_norm.jsonl
+    python tools/bench_svr_train.py --profile-encoder 20 --batches 128 --encoder-norm hip
 
-The last two are the programs of two `rocprofv3 --kernel-trace --stats` runs; tools/svr_train_split.py turns their kernel_stats.csv
+--encoder-norm: the values of ResNet.train_norm to measure ('library': BatchNorm2d / ReLU / add / max-pool on the library modules;
+'hip': the fused kernels of csrc/gwtf_norm2d.hip).  With more than one value every variant is built once per value and all of them
+are alternated in the one call; the profile programs take the first value.  norm2d_byte_model gives the bytes the fused kernels
+must move per pass, from the shapes alone: kernel time from a trace divides into it.
+
+The profile programs are the programs of two `rocprofv3 --kernel-trace --stats` runs; tools/svr_train_split.py turns their kernel_stats.csv
 files into the split of a step's kernel time between the image encoder's library kernels and everything else.
 """
 import argparse
@@ -37,6 +44,48 @@ from go_with_the_flows_amd.synth import calibrate_image_encoder, load_image_enco
 from go_with_the_flows_amd.training import GraphedTrainStep  # noqa: E402
 
 VARIANTS = ('list', 'fused', 'graphed')
+NORMS = ('library', 'hip')
+
+
+def norm2d_byte_model(B, H, W):
+    """Bytes the four kernel families of csrc/gwtf_norm2d.hip move in one forward + backward pass over the 20 BatchNorm2d layers of
+    the ResNet-18 encoder on (B, 4, H, W) images, counted from shapes (float32 activations, uint8 pool offsets; per-channel vectors
+    and partials left out).  Per layer of E elements (Ep pooled ones), reads + writes:
+        statistics        x                                             4 E
+        forward apply     x (+ residual) -> y                           8 E (12 E);  pool: x -> pooled y, offsets    4 E + 5 Ep
+        backward sums     x, dy (, saved y with ReLU)                   8 E (12 E);  pool: x, pooled dy, offsets     4 E + 5 Ep
+        backward apply    the same reads -> dx (+ d_residual)           +4 E (+8 E); pool                            8 E + 5 Ep
+    Returns {'activations', 'stats', 'apply_fwd', 'sums_bwd', 'apply_bwd', 'total'}."""
+    conv = lambda n, k, s, p: (n + 2 * p - k) // s + 1
+    h, w = conv(H, 7, 2, 3), conv(W, 7, 2, 3)
+    out = {'activations': 0, 'stats': 0, 'apply_fwd': 0, 'sums_bwd': 0, 'apply_bwd': 0}
+
+    def layer(E, relu=True, residual=False, Ep=0):
+        out['activations'] += E
+        out['stats'] += 4 * E
+        if Ep:
+            out['apply_fwd'] += 4 * E + 5 * Ep
+            out['sums_bwd'] += 4 * E + 5 * Ep
+            out['apply_bwd'] += 8 * E + 5 * Ep
+            return
+        reads = 8 * E + (4 * E if relu else 0)
+        out['apply_fwd'] += (12 if residual else 8) * E
+        out['sums_bwd'] += reads
+        out['apply_bwd'] += reads + (8 if residual else 4) * E
+
+    hp, wp = conv(h, 3, 2, 1), conv(w, 3, 2, 1)
+    layer(B * 64 * h * w, Ep=B * 64 * hp * wp)                      # stem
+    h, w = hp, wp
+    for C, stride in ((64, 1), (128, 2), (256, 2), (512, 2)):
+        h, w = conv(h, 3, stride, 1), conv(w, 3, stride, 1)
+        E = B * C * h * w
+        for block in range(2):
+            layer(E)                                                # bn1 -> relu
+            layer(E, residual=True)                                 # bn2 -> add -> relu
+        if stride != 1:
+            layer(E, relu=False)                                    # the downsample branch
+    out['total'] = out['stats'] + out['apply_fwd'] + out['sums_bwd'] + out['apply_bwd']
+    return out
 
 
 def config():
@@ -50,9 +99,11 @@ def make_optimizer(model, cfg):
 class Variant:
     """One way of taking a step, on its own copy of the model (same initial state) with its own optimiser."""
 
-    def __init__(self, kind, base_model, cfg, batch, noise=None):
-        self.kind, self.batch = kind, batch
+    def __init__(self, kind, base_model, cfg, batch, noise=None, norm='library'):
+        self.kind, self.batch, self.norm = kind, batch, norm
+        self.key = kind if norm == 'library' else f'{kind}/{norm}'
         self.model = copy.deepcopy(base_model)
+        self.model.img_encoder.train_norm = norm
         if noise is not None:
             self.model.reparameterize = lambda mu, logvar: noise * torch.exp(0.5 * logvar) + mu
         self.crit = models.Flow_Mixture_Loss(**cfg)
@@ -91,6 +142,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--variants', default=','.join(VARIANTS), help='comma-separated subset of list,fused,graphed')
+    ap.add_argument('--encoder-norm', default='library', help='comma-separated subset of library,hip (ResNet.train_norm)')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r21_svr_train.jsonl'))
     ap.add_argument('--profile-steps', type=int, default=0, metavar='N',
                     help='run N steps of the graphed variant at the first batch size and exit (the program of a kernel trace)')
@@ -100,6 +152,8 @@ def main():
     args = ap.parse_args()
     kinds = [k for k in args.variants.split(',') if k]
     assert all(k in VARIANTS for k in kinds), kinds
+    norms = [n for n in args.encoder_norm.split(',') if n]
+    assert norms and all(n in NORMS for n in norms), norms
     assert torch.cuda.is_available(), 'bench_svr_train needs a HIP device'
     dev, cfg = 'cuda:0', config()
     n_points, (H, W) = cfg['cloud_size'], cfg['image_size']
@@ -125,14 +179,16 @@ def main():
         batch = (g, p, imgs)
         if args.profile_encoder:
             enc = base.img_encoder
+            enc.train_norm = norms[0]
             for _ in range(args.profile_encoder):
                 enc.zero_grad(set_to_none=True)
                 enc(imgs).square().mean().backward()
             torch.cuda.synchronize()
-            print(json.dumps({'bench': 'svr_encoder_profile', 'B': B, 'steps': args.profile_encoder}), flush=True)
+            print(json.dumps({'bench': 'svr_encoder_profile', 'B': B, 'steps': args.profile_encoder, 'encoder_norm': norms[0],
+                              'norm2d_bytes_per_pass': norm2d_byte_model(B, H, W)}), flush=True)
             return
         if args.profile_steps:
-            v = Variant('graphed', base, cfg, batch)
+            v = Variant('graphed', base, cfg, batch, norm=norms[0])
             for _ in range(args.profile_steps):
                 v.step()
             torch.cuda.synchronize()
@@ -141,20 +197,27 @@ def main():
         noise = torch.randn(B, cfg['g_latent_space_size'], generator=torch.Generator().manual_seed(2323)).to(dev)
         terms = {}
         for kind in kinds:                      # one step each from the same state with the same noise: the same four numbers
-            v = Variant(kind, base, cfg, batch, noise)
-            terms[kind] = [float(t) for t in v.step()]
-            del v
+            for norm in norms:
+                v = Variant(kind, base, cfg, batch, noise, norm)
+                terms[v.key] = [float(t) for t in v.step()]
+                del v
         torch.cuda.empty_cache()
-        vs = [Variant(kind, base, cfg, batch) for kind in kinds]
+        vs = [Variant(kind, base, cfg, batch, norm=norm) for kind in kinds for norm in norms]
         for v in vs:
             for _ in range(args.warmup):
                 v.step()
-        ms = {kind: [] for kind in kinds}
+        ms = {v.key: [] for v in vs}
         for _ in range(args.repeats):           # alternated: a drift of the machine hits every variant alike
             for v in vs:
-                ms[v.kind].append(round(v.timed(args.steps), 3))
+                ms[v.key].append(round(v.timed(args.steps), 3))
         rec = {'bench': 'svr_train_step', 'B': B, 'n_points': n_points, 'image': [H, W], 'K': cfg['n_components'],
                'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms, 'terms_loss_pnll_gnll_gent': terms}
+        if 'graphed' in ms and 'graphed/hip' in ms:
+            rec['encoder_norm'] = norms
+            rec['graphed_library_over_hip'] = (round(min(ms['graphed']) / max(ms['graphed/hip']), 3),
+                                               round(max(ms['graphed']) / min(ms['graphed/hip']), 3))
+            rec['hip_faster_beyond_spread'] = max(ms['graphed/hip']) < min(ms['graphed'])
+            rec['hip_slower_beyond_spread'] = min(ms['graphed/hip']) > max(ms['graphed'])
         if 'list' in ms and 'graphed' in ms:
             rec['list_over_graphed'] = round(min(ms['list']) / max(ms['graphed']), 3), round(max(ms['list']) / min(ms['graphed']), 3)
             rec['graphed_faster_beyond_spread'] = max(ms['graphed']) < min(ms['list'])
