@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GWTF_LIB') or os.path.join(_HERE, 'libgwtf_hip.so')      # GWTF_LIB: an A/B build (tools/ab_build.sh)
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 MODE_DIRECT, MODE_INVERSE = 0, 1
 STAT_REPLICAS = 64   # GWTF_STAT_REPLICAS in csrc/gwtf_layout.h
@@ -34,10 +34,8 @@ _SIGNATURES = {
     'gwtf_pack_weights_exact': (ctypes.c_int, [_c_fp, _c_fp, _c_fp] + [ctypes.c_int] * 5 + [_c_fp]),
     'gwtf_stack_forward_exact': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'gwtf_latent_loss_workspace_floats': (ctypes.c_int, [ctypes.c_int] * 2),
-    'gwtf_latent_loss_forward': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 3 + [ctypes.c_float] * 3 + [_c_fp]),
-    'gwtf_latent_loss_backward': (ctypes.c_int, [_c_fp] * 10 + [ctypes.c_int] * 3 + [ctypes.c_float] * 3 + [_c_fp]),
-    'gwtf_latent_loss_rows_forward': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 3 + [ctypes.c_float] * 3 + [_c_fp]),
-    'gwtf_latent_loss_rows_backward': (ctypes.c_int, [_c_fp] * 10 + [ctypes.c_int] * 3 + [ctypes.c_float] * 3 + [_c_fp]),
+    'gwtf_latent_loss_forward': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_latent_loss_backward': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_stack_plan': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]),
     'gwtf_bwd_plan': (ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_int)]),
     'gwtf_pack_w1t': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_fp]),
@@ -96,12 +94,8 @@ _SIGNATURES = {
     'gwtf_mtrain_final_forward_half': (ctypes.c_int, [ctypes.c_int]),
     'gwtf_mtrain_final_backward_half': (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     'gwtf_head_layer_supported': (ctypes.c_int, [ctypes.c_int] * 4),
-    'gwtf_head_layer_forward': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_float, ctypes.c_float] + [ctypes.c_int] * 3 + [_c_fp] * 3 +
-                                [ctypes.c_int] * 3 + [_c_fp]),
-    'gwtf_head_layer_backward': (ctypes.c_int, [_c_fp] * 9 + [ctypes.c_int] * 2 + [_c_fp] * 2 + [ctypes.c_int] + [_c_fp] * 4 +
-                                 [ctypes.c_int] * 3 + [_c_fp]),
-    'gwtf_head_pair_forward': (ctypes.c_int, [_c_fp] * 9 + [ctypes.c_int] * 4 + [_c_fp]),
-    'gwtf_head_pair_backward': (ctypes.c_int, [_c_fp] * 18 + [ctypes.c_int] * 4 + [_c_fp]),
+    'gwtf_heads_forward': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_heads_backward': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_resnet_packed_floats': (ctypes.c_size_t, [ctypes.c_int]),
     'gwtf_resnet_work_floats': (ctypes.c_size_t, [ctypes.c_int] * 4),
     'gwtf_resnet_forward': (ctypes.c_int, [_c_fp] * 4 + [ctypes.c_int] * 5 + [_c_fp]),
@@ -132,7 +126,21 @@ class TrainCtx(ctypes.Structure):
 ENC_PHASE_FWD_INIT, ENC_PHASE_FWD_LAYER, ENC_PHASE_BWD_TOP, ENC_PHASE_BWD_LAYER = range(4)
 
 
-class EncTrainCtx(ctypes.Structure):
+class _Binds:
+    """A record whose pointer fields are filled from tensors by name."""
+
+    def bind(self, bufs):
+        """self.<name> = the device address of bufs[name]: a tensor, or a list of tensors for the leading entries of an array field
+        (None: NULL)."""
+        at = lambda b: None if b is None else b.data_ptr()
+        for name, b in bufs.items():
+            if isinstance(b, (list, tuple)):
+                getattr(self, name)[:len(b)] = [at(e) for e in b]
+            else:
+                setattr(self, name, at(b))
+
+
+class EncTrainCtx(_Binds, ctypes.Structure):
     """GwtfEncTrainCtx of include/gwtf.h (the encoder's train pipeline, both directions): same field order."""
     _p, _p2, _p3, _p4 = ctypes.c_void_p, ctypes.c_void_p * 2, ctypes.c_void_p * 3, ctypes.c_void_p * 4
     _fields_ = [('B', ctypes.c_int), ('N', ctypes.c_int), ('n_total', ctypes.c_double), ('momentum', ctypes.c_float * 4),
@@ -144,14 +152,22 @@ class EncTrainCtx(ctypes.Structure):
                 ('units_m', _p), ('mconst', _p), ('mform_ws', _p), ('extra', _p), ('slot_of', _p), ('tables', _p), ('a2rows', _p),
                 ('dA', _p2), ('partials', _p), ('gram', _p), ('S', _p), ('dW', _p4), ('stream', _p)]
 
-    def bind(self, bufs):
-        """self.<name> = the device address of bufs[name]: a tensor, or a list of tensors for a per-layer array field (None: NULL)."""
-        at = lambda b: None if b is None else b.data_ptr()
-        for name, b in bufs.items():
-            if isinstance(b, (list, tuple)):
-                getattr(self, name)[:] = [at(e) for e in b]
-            else:
-                setattr(self, name, at(b))
+
+class HeadArgs(_Binds, ctypes.Structure):
+    """GwtfHeadArgs of include/gwtf.h (one or two head layers on the same input, either direction): same field order."""
+    _fields_ = ([('x', ctypes.c_void_p), ('g_x', ctypes.c_void_p)] + [(n, ctypes.c_int) for n in ('n_heads', 'B', 'Din', 'bn_updates')] +
+                [(n, ctypes.c_void_p * 2) for n in ('W', 'bias', 'gamma', 'beta', 'running_mean', 'running_var', 'num_batches_tracked',
+                                                    'ypre', 'stats', 'out', 'g_out', 'g_y', 'g_W', 'g_bias', 'g_gamma', 'g_beta')] +
+                [(n, ctypes.c_int * 2) for n in ('Dout', 'bn_mode', 'act')] + [(n, ctypes.c_float * 2) for n in ('momentum', 'bn_eps')] +
+                [('stream', ctypes.c_void_p)])
+
+
+class LatentLossArgs(_Binds, ctypes.Structure):
+    """GwtfLatentLossArgs of include/gwtf.h (the latent loss terms, either direction and either family): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('nll', 'z', 'mu0', 'lv0', 'flow_lv', 'post_lv', 'workspace', 'out4', 'g_out4', 'g_nll',
+                                                'g_z', 'g_mu0', 'g_lv0', 'g_flow_lv', 'g_post_lv')] +
+                [(n, ctypes.c_int) for n in ('B', 'G', 'n2', 'rows')] + [(n, ctypes.c_float) for n in ('pw', 'gw', 'ew')] +
+                [('stream', ctypes.c_void_p)])
 
 
 class StackArgs(ctypes.Structure):

@@ -5,7 +5,8 @@
 // library launches per step (Linear, batch_norm, sigmoid, mul, ... and their autograd) on the critical path between the
 // encoder and the decoders.
 //
-// ONE LAYER per launch, forward and backward:
+// ONE LAYER per launch, forward and backward -- or TWO layers on the same input (the mu / logvar heads of a FeatureEncoder, reference
+// encoders.py:55-60): a launch takes one record (include/gwtf.h GwtfHeadArgs) of 1 or 2 heads; the blocks of head 0 come first:
 //   forward : y = x W^T (+ bias) -> [BatchNorm over the B rows: batch statistics, running statistics updated `bn_updates` times,
 //             or running statistics] -> [Swish | log-softmax].  A workgroup owns 16 output COLUMNS and all rows: everything
 //             BatchNorm needs (column statistics) is local to it -- no grid-wide barrier; Dout / 16 workgroups (the exact-fp32 MFMA makes wider blocks throughput-bound on one CU).
@@ -133,25 +134,29 @@ __device__ __forceinline__ void head_fwd_block(int bid, HeadDims d, const float*
   }
 }
 
-__global__ __launch_bounds__(kThreads) void head_fwd_kernel(HeadDims d, const float* __restrict__ x, const float* __restrict__ W,
-                                                            const float* __restrict__ bias, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, float* __restrict__ rmean,
-                                                            float* __restrict__ rvar, long long* __restrict__ nbt, float momentum,
-                                                            float bn_eps, int bn_mode, int bn_updates, int act,
-                                                            float* __restrict__ ypre, float* __restrict__ stats,
-                                                            float* __restrict__ out) {
-  head_fwd_block(blockIdx.x, d, x, W, bias, gamma, beta, rmean, rvar, nbt, momentum, bn_eps, bn_mode, bn_updates, act, ypre, stats, out);
+// The three kernels are instantiated for records of one head and of two (the launchers choose by n_heads): with one head every
+// field is read at a fixed place of the record; with two, a workgroup of the forward / of pass 1 finds its head from its index --
+// blocks [0, ceil(Dout[0] / 16)) are head 0's column blocks, the rest head 1's -- and reads that head's entries, one dependent fetch
+// more (0.2 us per launch, measured over the launches of a graphed module at these kernels' 5-20 us).  kPlain: every head of the
+// record is a plain Linear (bn_mode 0, act 0: the mu / logvar pair) -- the same body with both known at compile time (0.3 us per
+// launch); the launchers choose it for two plain heads.
+struct HeadBlock { int h, bid; };
+template <int kHeads>
+__device__ __forceinline__ HeadBlock head_block(const GwtfHeadArgs& a) {
+  if (kHeads == 1) return {0, (int)blockIdx.x};
+  const int n0 = (a.Dout[0] + kCols - 1) / kCols;
+  const int h = (int)blockIdx.x < n0 ? 0 : 1;
+  return {h, (int)blockIdx.x - (h ? n0 : 0)};
 }
 
-// TWO plain Linear heads on the same input (the mu / logvar heads of a FeatureEncoder, reference encoders.py:55-60) in one launch:
-// blocks [0, ceil(Dout_a / 16)) are head a's column blocks, the rest head b's
-struct HeadPair { const float* W[2]; const float* bias[2]; float* ypre[2]; float* out[2]; int Dout[2]; };
-__global__ __launch_bounds__(kThreads) void head_fwd_pair_kernel(int B, int Din, const float* __restrict__ x, HeadPair hp) {
-  const int na = (hp.Dout[0] + kCols - 1) / kCols;
-  const int h = (int)blockIdx.x < na ? 0 : 1, bid = (int)blockIdx.x - (h ? na : 0);
-  const HeadDims d = {B, Din, hp.Dout[h]};
-  head_fwd_block(bid, d, x, hp.W[h], hp.bias[h], nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 1e-5f, 0, 1, 0, hp.ypre[h], nullptr,
-                 hp.out[h]);
+template <int kHeads, bool kPlain>
+__global__ __launch_bounds__(kThreads) void head_fwd_kernel(const GwtfHeadArgs a) {
+  const HeadBlock hb = head_block<kHeads>(a);
+  const int h = hb.h;
+  const HeadDims d = {a.B, a.Din, a.Dout[h]};
+  head_fwd_block(hb.bid, d, a.x, a.W[h], a.bias[h], a.gamma[h], a.beta[h], a.running_mean[h], a.running_var[h],
+                 a.num_batches_tracked[h], a.momentum[h], a.bn_eps[h], kPlain ? 0 : a.bn_mode[h], a.bn_updates, kPlain ? 0 : a.act[h],
+                 a.ypre[h], a.stats[h], a.out[h]);
 }
 
 // ---- backward, pass 1: per block of 16 output columns ---------------------------------------------------------------------------
@@ -273,45 +278,61 @@ __device__ __forceinline__ void head_bwd1_block(int bid, HeadDims d, const float
   }
 }
 
-__global__ __launch_bounds__(kThreads) void head_bwd1_kernel(HeadDims d, const float* __restrict__ x, const float* __restrict__ bias,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             const float* __restrict__ ypre, const float* __restrict__ stats,
-                                                             const float* __restrict__ out, const float* __restrict__ g_out,
-                                                             int bn_mode, int act, float* __restrict__ g_y, float* __restrict__ g_W,
-                                                             float* __restrict__ g_bias, float* __restrict__ g_gamma,
-                                                             float* __restrict__ g_beta) {
-  head_bwd1_block(blockIdx.x, d, x, bias, gamma, beta, ypre, stats, out, g_out, bn_mode, act, g_y, g_W, g_bias, g_gamma, g_beta);
+template <int kHeads, bool kPlain>
+__global__ __launch_bounds__(kThreads) void head_bwd1_kernel(const GwtfHeadArgs a) {
+  const HeadBlock hb = head_block<kHeads>(a);
+  const int h = hb.h;
+  const HeadDims d = {a.B, a.Din, a.Dout[h]};
+  head_bwd1_block(hb.bid, d, a.x, a.bias[h], a.gamma[h], a.beta[h], a.ypre[h], a.stats[h], a.out[h], a.g_out[h],
+                  kPlain ? 0 : a.bn_mode[h], kPlain ? 0 : a.act[h], a.g_y[h], a.g_W[h], a.g_bias[h], a.g_gamma[h], a.g_beta[h]);
 }
 
-struct HeadPairBwd { const float* bias[2]; const float* ypre[2]; const float* out[2]; const float* g_out[2]; float* g_y[2]; float* g_W[2];
-                     float* g_bias[2]; const float* W[2]; int Dout[2]; };
-__global__ __launch_bounds__(kThreads) void head_bwd1_pair_kernel(int B, int Din, const float* __restrict__ x, HeadPairBwd hp) {
-  const int na = (hp.Dout[0] + kCols - 1) / kCols;
-  const int h = (int)blockIdx.x < na ? 0 : 1, bid = (int)blockIdx.x - (h ? na : 0);
-  const HeadDims d = {B, Din, hp.Dout[h]};
-  head_bwd1_block(bid, d, x, hp.bias[h], nullptr, nullptr, hp.ypre[h], nullptr, hp.out[h], hp.g_out[h], 0, 0, hp.g_y[h], hp.g_W[h],
-                  hp.g_bias[h], nullptr, nullptr);
-}
-
-// ---- backward, pass 2: per block of 16 input columns: g_x[:, block] (+)= g_y W[:, block] ------------------------------------------
-__global__ __launch_bounds__(kThreads) void head_bwd2_kernel(HeadDims d, const float* __restrict__ W, const float* __restrict__ g_y,
-                                                             float* __restrict__ g_x, int accumulate) {
-  const int c0 = blockIdx.x * kCols, nc = min(kCols, d.Din - c0);
+// ---- backward, pass 2: per block of 16 input columns: g_x[:, block] = sum over the heads of g_y W[:, block] (the second head's product
+// accumulates onto the first's) --------------------------------------------------------------------------------------------------
+template <int kHeads>
+__global__ __launch_bounds__(kThreads) void head_bwd2_kernel(const GwtfHeadArgs a) {
+  const int c0 = blockIdx.x * kCols, nc = min(kCols, a.Din - c0);
   __shared__ float work[kWorkFloats];
-  head_gemm(d.B, nc, d.Dout, g_y, d.Dout, 1, W + c0, 1, d.Din, g_x + c0, d.Din, accumulate != 0, work);
-}
-
-// the pair's input gradient: g_x[:, block] = g_ya Wa[:, block] + g_yb Wb[:, block] (the second product accumulates onto the first)
-__global__ __launch_bounds__(kThreads) void head_bwd2_pair_kernel(int B, int Din, HeadPairBwd hp, float* __restrict__ g_x) {
-  const int c0 = blockIdx.x * kCols, nc = min(kCols, Din - c0);
-  __shared__ float work[kWorkFloats];
-  head_gemm(B, nc, hp.Dout[0], hp.g_y[0], hp.Dout[0], 1, hp.W[0] + c0, 1, Din, g_x + c0, Din, false, work);
-  phase_sync();
-  head_gemm(B, nc, hp.Dout[1], hp.g_y[1], hp.Dout[1], 1, hp.W[1] + c0, 1, Din, g_x + c0, Din, true, work);
+#pragma unroll
+  for (int h = 0; h < kHeads; ++h) {
+    if (h) phase_sync();
+    head_gemm(a.B, nc, a.Dout[h], a.g_y[h], a.Dout[h], 1, a.W[h] + c0, 1, a.Din, a.g_x + c0, a.Din, h > 0, work);
+  }
 }
 
 constexpr int kMaxRows = 1 << 16;   // any batch: the kernels walk it in blocks of 64 / 128 rows
 bool dims_ok(int B, int Din, int Dout) { return B >= 1 && B <= kMaxRows && Din >= 1 && Dout >= 1 && Din <= 4096 && Dout <= 4096; }
+
+// the record's checks (include/gwtf.h), host only
+bool heads_ok(const GwtfHeadArgs* a, bool backward) {
+  if (!a || a->n_heads < 1 || a->n_heads > 2 || !a->x || a->bn_updates < 1) return false;
+  for (int h = 0; h < a->n_heads; ++h) {
+    const int mode = a->bn_mode[h], act = a->act[h];
+    if (!a->W[h] || !a->ypre[h] || !a->out[h] || (backward && (!a->g_out[h] || !a->g_y[h])) || !dims_ok(a->B, a->Din, a->Dout[h]) ||
+        mode < 0 || mode > 2 || act < 0 || act > 2 || (mode != 0 && !a->stats[h]) ||
+        (mode == 2 && (!a->running_mean[h] || !a->running_var[h])) || (act == 2 && a->Dout[h] > kCols) || (mode == 1 && a->B < 2))
+      return false;
+  }
+  return true;
+}
+
+// column blocks of all heads: the grid of the forward and of pass 1
+int head_blocks(const GwtfHeadArgs* a) {
+  int n = 0;
+  for (int h = 0; h < a->n_heads; ++h) n += (a->Dout[h] + kCols - 1) / kCols;
+  return n;
+}
+
+// the instantiation of a forward / pass 1 kernel for a record: one head, two heads, two plain Linear heads
+using HeadKernel = void (*)(const GwtfHeadArgs);
+template <template <int, bool> class K>
+HeadKernel head_kernel(const GwtfHeadArgs* a) {
+  if (a->n_heads == 1) return K<1, false>::fn;
+  const bool plain = a->bn_mode[0] == 0 && a->act[0] == 0 && a->bn_mode[1] == 0 && a->act[1] == 0;
+  return plain ? K<2, true>::fn : K<2, false>::fn;
+}
+template <int kHeads, bool kPlain> struct Fwd { static constexpr HeadKernel fn = head_fwd_kernel<kHeads, kPlain>; };
+template <int kHeads, bool kPlain> struct Bwd1 { static constexpr HeadKernel fn = head_bwd1_kernel<kHeads, kPlain>; };
 
 }  // namespace
 
@@ -319,62 +340,18 @@ extern "C" int gwtf_head_layer_supported(int B, int Din, int Dout, int act) {
   return dims_ok(B, Din, Dout) && (act != 2 || Dout <= kCols) ? 1 : 0;
 }
 
-extern "C" int gwtf_head_layer_forward(const float* x, const float* W, const float* bias, const float* gamma, const float* beta,
-                                       float* running_mean, float* running_var, long long* num_batches_tracked, float momentum,
-                                       float bn_eps, int bn_mode, int bn_updates, int act, float* ypre, float* stats, float* out,
-                                       int B, int Din, int Dout, void* stream) {
-  if (!x || !W || !ypre || !out || !dims_ok(B, Din, Dout) || bn_mode < 0 || bn_mode > 2 || act < 0 || act > 2 ||
-      (bn_mode != 0 && !stats) || (bn_mode == 2 && (!running_mean || !running_var)) || (act == 2 && Dout > kCols) ||
-      (bn_mode == 1 && B < 2) || bn_updates < 1)
-    return GWTF_E_BADARG;
-  const HeadDims d = {B, Din, Dout};
-  hipLaunchKernelGGL(head_fwd_kernel, dim3((Dout + kCols - 1) / kCols), dim3(kThreads), 0, (hipStream_t)stream, d, x, W, bias, gamma,
-                     beta, running_mean, running_var, num_batches_tracked, momentum, bn_eps, bn_mode, bn_updates, act, ypre, stats,
-                     out);
+extern "C" int gwtf_heads_forward(const GwtfHeadArgs* a) {
+  if (!heads_ok(a, false)) return GWTF_E_BADARG;
+  hipLaunchKernelGGL(head_kernel<Fwd>(a), dim3(head_blocks(a)), dim3(kThreads), 0, (hipStream_t)a->stream, *a);
   return (int)hipGetLastError();
 }
 
-extern "C" int gwtf_head_layer_backward(const float* x, const float* W, const float* bias, const float* gamma, const float* beta,
-                                        const float* ypre, const float* stats, const float* out, const float* g_out, int bn_mode,
-                                        int act, float* g_y, float* g_x, int accumulate_g_x, float* g_W, float* g_bias,
-                                        float* g_gamma, float* g_beta, int B, int Din, int Dout, void* stream) {
-  if (!x || !W || !ypre || !out || !g_out || !g_y || !dims_ok(B, Din, Dout) || bn_mode < 0 || bn_mode > 2 || act < 0 || act > 2 ||
-      (bn_mode != 0 && !stats) || (act == 2 && Dout > kCols))
-    return GWTF_E_BADARG;
-  const HeadDims d = {B, Din, Dout};
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(head_bwd1_kernel, dim3((Dout + kCols - 1) / kCols), dim3(kThreads), 0, st, d, x, bias, gamma, beta, ypre, stats,
-                     out, g_out, bn_mode, act, g_y, g_W, g_bias, g_gamma, g_beta);
-  if (g_x)
-    hipLaunchKernelGGL(head_bwd2_kernel, dim3((Din + kCols - 1) / kCols), dim3(kThreads), 0, st, d, W, g_y, g_x, accumulate_g_x);
-  return (int)hipGetLastError();
-}
-
-// see include/gwtf.h
-extern "C" int gwtf_head_pair_forward(const float* x, const float* Wa, const float* bias_a, const float* Wb, const float* bias_b,
-                                      float* ypre_a, float* out_a, float* ypre_b, float* out_b, int B, int Din, int Dout_a, int Dout_b,
-                                      void* stream) {
-  if (!x || !Wa || !Wb || !ypre_a || !out_a || !ypre_b || !out_b || !dims_ok(B, Din, Dout_a) || !dims_ok(B, Din, Dout_b))
-    return GWTF_E_BADARG;
-  HeadPair hp = {{Wa, Wb}, {bias_a, bias_b}, {ypre_a, ypre_b}, {out_a, out_b}, {Dout_a, Dout_b}};
-  const int blocks = (Dout_a + kCols - 1) / kCols + (Dout_b + kCols - 1) / kCols;
-  hipLaunchKernelGGL(head_fwd_pair_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, B, Din, x, hp);
-  return (int)hipGetLastError();
-}
-
-extern "C" int gwtf_head_pair_backward(const float* x, const float* Wa, const float* bias_a, const float* Wb, const float* bias_b,
-                                       const float* ypre_a, const float* out_a, const float* ypre_b, const float* out_b,
-                                       const float* g_out_a, const float* g_out_b, float* g_y_a, float* g_y_b, float* g_x, float* g_Wa,
-                                       float* g_bias_a, float* g_Wb, float* g_bias_b, int B, int Din, int Dout_a, int Dout_b,
-                                       void* stream) {
-  if (!x || !Wa || !Wb || !ypre_a || !out_a || !ypre_b || !out_b || !g_out_a || !g_out_b || !g_y_a || !g_y_b ||
-      !dims_ok(B, Din, Dout_a) || !dims_ok(B, Din, Dout_b))
-    return GWTF_E_BADARG;
-  HeadPairBwd hp = {{bias_a, bias_b}, {ypre_a, ypre_b}, {out_a, out_b}, {g_out_a, g_out_b}, {g_y_a, g_y_b}, {g_Wa, g_Wb},
-                    {g_bias_a, g_bias_b}, {Wa, Wb}, {Dout_a, Dout_b}};
-  hipStream_t st = (hipStream_t)stream;
-  const int blocks = (Dout_a + kCols - 1) / kCols + (Dout_b + kCols - 1) / kCols;
-  hipLaunchKernelGGL(head_bwd1_pair_kernel, dim3(blocks), dim3(kThreads), 0, st, B, Din, x, hp);
-  if (g_x) hipLaunchKernelGGL(head_bwd2_pair_kernel, dim3((Din + kCols - 1) / kCols), dim3(kThreads), 0, st, B, Din, hp, g_x);
+extern "C" int gwtf_heads_backward(const GwtfHeadArgs* a) {
+  if (!heads_ok(a, true)) return GWTF_E_BADARG;
+  hipStream_t st = (hipStream_t)a->stream;
+  hipLaunchKernelGGL(head_kernel<Bwd1>(a), dim3(head_blocks(a)), dim3(kThreads), 0, st, *a);
+  if (a->g_x)
+    hipLaunchKernelGGL(a->n_heads == 1 ? head_bwd2_kernel<1> : head_bwd2_kernel<2>, dim3((a->Din + kCols - 1) / kCols), dim3(kThreads), 0,
+                       st, *a);
   return (int)hipGetLastError();
 }

@@ -5,9 +5,10 @@
 //     pnll = sum_b nll_b / B            loss = pw pnll + gw gnll - ew gent
 // As torch ops these are ~25 elementwise / reduction launches forward and ~30 backward on (B, G) tensors of a few thousand elements:
 // 0.15 ms of a 9 ms step spent on launch latency.
-// Two families: the base Gaussian shared by the batch (mu0, lv0 [G]: the generative / autoencoding models' learned parameters) and
-// one base Gaussian per row (mu0, lv0 [B][G]: the single-view reconstruction model's g0_prior(img_encoder(images))); the `rows`
-// family reads mu0[e] / lv0[e] where the shared one reads mu0[e % G], and its backward has no column sums.
+// One record (include/gwtf.h GwtfLatentLossArgs), two families by its `rows` field: the base Gaussian shared by the batch (mu0, lv0
+// [G]: the generative / autoencoding models' learned parameters) and one base Gaussian per row (mu0, lv0 [B][G]: the single-view
+// reconstruction model's g0_prior(img_encoder(images))); the per-row family reads mu0[e] / lv0[e] where the shared one reads
+// mu0[e % G], and its backward has no column sums.
 #include <hip/hip_runtime.h>
 #include "../../include/gwtf.h"
 
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(kThreads) void latent_finish_kernel(const float* __
 }
 
 // g_out[4] = upstream of {loss, pnll, gnll, gent}.  Blocks [0, nb_e): elementwise part; the rest: the column sums of mu0 / lv0.
-__global__ __launch_bounds__(256) void latent_bwd_kernel(const float* __restrict__ g_out, const float* __restrict__ z,
+__global__ __launch_bounds__(kThreads) void latent_bwd_kernel(const float* __restrict__ g_out, const float* __restrict__ z,
                                                          const float* __restrict__ mu0, const float* __restrict__ lv0,
                                                          float* __restrict__ g_nll, float* __restrict__ g_z, float* __restrict__ g_mu0,
                                                          float* __restrict__ g_lv0, float* __restrict__ g_flow, float* __restrict__ g_post,
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(const float* __restrict
   const float cp = (gl * pw + g_out[1]) / (float)B, cg = (gl * gw + g_out[2]) / (float)B, ce = (g_out[3] - gl * ew) / (float)B;
   const int n = B * G;
   if ((int)blockIdx.x < nb_e) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
+    const int e = blockIdx.x * kThreads + threadIdx.x;
     if (e < B) g_nll[e] = cp;
     if (e >= n) return;
     const int j = e % G;
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(const float* __restrict
     for (int l = 0; l < n2; ++l) g_flow[(size_t)l * n + e] = c;
     return;
   }
-  const int j = ((int)blockIdx.x - nb_e) * 256 + threadIdx.x;
+  const int j = ((int)blockIdx.x - nb_e) * kThreads + threadIdx.x;
   if (j >= G) return;
   const float m = mu0[j], r = __expf(-lv0[j]);
   float sm = 0.f, sl = 0.f;
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(const float* __restrict
 }
 
 // per-row base: every gradient is elementwise (mu0 / lv0 have the shape of z), one element per thread
-__global__ __launch_bounds__(256) void latent_rows_bwd_kernel(const float* __restrict__ g_out, const float* __restrict__ z,
+__global__ __launch_bounds__(kThreads) void latent_rows_bwd_kernel(const float* __restrict__ g_out, const float* __restrict__ z,
                                                               const float* __restrict__ mu0, const float* __restrict__ lv0,
                                                               float* __restrict__ g_nll, float* __restrict__ g_z,
                                                               float* __restrict__ g_mu0, float* __restrict__ g_lv0,
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(256) void latent_rows_bwd_kernel(const float* __res
                                                               int n2, float pw, float gw, float ew) {
   const float gl = g_out[0];
   const float cp = (gl * pw + g_out[1]) / (float)B, cg = (gl * gw + g_out[2]) / (float)B, ce = (g_out[3] - gl * ew) / (float)B;
-  const int n = B * G, e = blockIdx.x * 256 + threadIdx.x;
+  const int n = B * G, e = blockIdx.x * kThreads + threadIdx.x;
   if (e < B) g_nll[e] = cp;
   if (e >= n) return;
   const float d = z[e] - mu0[e], r = __expf(-lv0[e]);
@@ -137,61 +138,44 @@ __global__ __launch_bounds__(256) void latent_rows_bwd_kernel(const float* __res
   for (int l = 0; l < n2; ++l) g_flow[(size_t)l * n + e] = c;
 }
 
-// B * G elements in blocks of kThreads: 0 when the product does not fit an int (the element index of the kernels)
+// B * G elements in blocks of kThreads: 0 when there are none or the product does not fit an int (the element index of the kernels)
 int latent_blocks(int B, int G) {
   const long long n = (long long)B * G;
-  return n > 0x7fffffffLL - kThreads ? 0 : (int)((n + kThreads - 1) / kThreads);
+  return B <= 0 || G <= 0 || n > 0x7fffffffLL - kThreads ? 0 : (int)((n + kThreads - 1) / kThreads);
 }
+
+// the sizes and the family of a record, before its pointers: 0 blocks = refused
+int latent_blocks(const GwtfLatentLossArgs* a) { return !a || a->n2 <= 0 || a->rows < 0 || a->rows > 1 ? 0 : latent_blocks(a->B, a->G); }
 
 }  // namespace
 
-extern "C" int gwtf_latent_loss_workspace_floats(int B, int G) { return 2 * ((B * G + kThreads - 1) / kThreads); }
+extern "C" int gwtf_latent_loss_workspace_floats(int B, int G) { return 2 * latent_blocks(B, G); }
 
-extern "C" int gwtf_latent_loss_forward(const float* nll, const float* z, const float* mu0, const float* lv0, const float* flow_lv,
-                                        const float* post_lv, float* workspace, float* out4, int B, int G, int n2, float pw, float gw,
-                                        float ew, void* stream) {
-  if (!nll || !z || !mu0 || !lv0 || !flow_lv || !post_lv || !workspace || !out4 || B <= 0 || G <= 0 || n2 <= 0) return GWTF_E_BADARG;
-  const int nb = (B * G + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(latent_part_kernel<false>, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, z, mu0, lv0, flow_lv, post_lv,
-                     (float2*)workspace, B, G, n2);
-  hipLaunchKernelGGL(latent_finish_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, nll, (const float2*)workspace, out4, B, G,
-                     nb, pw, gw, ew);
+extern "C" int gwtf_latent_loss_forward(const GwtfLatentLossArgs* a) {
+  const int nb = latent_blocks(a);
+  if (nb == 0 || !a->nll || !a->z || !a->mu0 || !a->lv0 || !a->flow_lv || !a->post_lv || !a->workspace || !a->out4) return GWTF_E_BADARG;
+  hipStream_t st = (hipStream_t)a->stream;
+  float2* part = (float2*)a->workspace;
+  hipLaunchKernelGGL(a->rows == 0 ? latent_part_kernel<false> : latent_part_kernel<true>, dim3(nb), dim3(kThreads), 0, st, a->z, a->mu0, a->lv0,
+                     a->flow_lv, a->post_lv, part, a->B, a->G, a->n2);
+  hipLaunchKernelGGL(latent_finish_kernel, dim3(1), dim3(kThreads), 0, st, a->nll, (const float2*)part, a->out4, a->B, a->G, nb, a->pw,
+                     a->gw, a->ew);
   return (int)hipGetLastError();
 }
 
-extern "C" int gwtf_latent_loss_backward(const float* g_out4, const float* z, const float* mu0, const float* lv0, float* g_nll,
-                                         float* g_z, float* g_mu0, float* g_lv0, float* g_flow_lv, float* g_post_lv, int B, int G,
-                                         int n2, float pw, float gw, float ew, void* stream) {
-  if (!g_out4 || !z || !mu0 || !lv0 || !g_nll || !g_z || !g_mu0 || !g_lv0 || !g_flow_lv || !g_post_lv || B <= 0 || G <= 0 || n2 <= 0)
+extern "C" int gwtf_latent_loss_backward(const GwtfLatentLossArgs* a) {
+  const int nb = latent_blocks(a);
+  if (nb == 0 || !a->g_out4 || !a->z || !a->mu0 || !a->lv0 || !a->g_nll || !a->g_z || !a->g_mu0 || !a->g_lv0 || !a->g_flow_lv ||
+      !a->g_post_lv)
     return GWTF_E_BADARG;
-  const int nb_e = (B * G + 255) / 256, nb_c = (G + 255) / 256;
-  hipLaunchKernelGGL(latent_bwd_kernel, dim3(nb_e + nb_c), dim3(256), 0, (hipStream_t)stream, g_out4, z, mu0, lv0, g_nll, g_z, g_mu0,
-                     g_lv0, g_flow_lv, g_post_lv, B, G, n2, pw, gw, ew, nb_e);
-  return (int)hipGetLastError();
-}
-
-// ---- one base Gaussian per row: mu0, lv0 (and their gradients) are [B][G] ---------------------------------------------------------------
-extern "C" int gwtf_latent_loss_rows_forward(const float* nll, const float* z, const float* mu0, const float* lv0, const float* flow_lv,
-                                             const float* post_lv, float* workspace, float* out4, int B, int G, int n2, float pw,
-                                             float gw, float ew, void* stream) {
-  if (!nll || !z || !mu0 || !lv0 || !flow_lv || !post_lv || !workspace || !out4 || B <= 0 || G <= 0 || n2 <= 0) return GWTF_E_BADARG;
-  const int nb = latent_blocks(B, G);
-  if (nb == 0) return GWTF_E_BADARG;
-  hipLaunchKernelGGL(latent_part_kernel<true>, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, z, mu0, lv0, flow_lv, post_lv,
-                     (float2*)workspace, B, G, n2);
-  hipLaunchKernelGGL(latent_finish_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, nll, (const float2*)workspace, out4, B, G,
-                     nb, pw, gw, ew);
-  return (int)hipGetLastError();
-}
-
-extern "C" int gwtf_latent_loss_rows_backward(const float* g_out4, const float* z, const float* mu0, const float* lv0, float* g_nll,
-                                              float* g_z, float* g_mu0, float* g_lv0, float* g_flow_lv, float* g_post_lv, int B, int G,
-                                              int n2, float pw, float gw, float ew, void* stream) {
-  if (!g_out4 || !z || !mu0 || !lv0 || !g_nll || !g_z || !g_mu0 || !g_lv0 || !g_flow_lv || !g_post_lv || B <= 0 || G <= 0 || n2 <= 0)
-    return GWTF_E_BADARG;
-  const int nb = latent_blocks(B, G);
-  if (nb == 0) return GWTF_E_BADARG;
-  hipLaunchKernelGGL(latent_rows_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, g_out4, z, mu0, lv0, g_nll, g_z, g_mu0, g_lv0,
-                     g_flow_lv, g_post_lv, B, G, n2, pw, gw, ew);
+  hipStream_t st = (hipStream_t)a->stream;
+  if (a->rows) {
+    hipLaunchKernelGGL(latent_rows_bwd_kernel, dim3(nb), dim3(kThreads), 0, st, a->g_out4, a->z, a->mu0, a->lv0, a->g_nll, a->g_z,
+                       a->g_mu0, a->g_lv0, a->g_flow_lv, a->g_post_lv, a->B, a->G, a->n2, a->pw, a->gw, a->ew);
+  } else {
+    const int nb_c = (a->G + kThreads - 1) / kThreads;      // the column sums of mu0 / lv0 behind the elementwise blocks
+    hipLaunchKernelGGL(latent_bwd_kernel, dim3(nb + nb_c), dim3(kThreads), 0, st, a->g_out4, a->z, a->mu0, a->lv0, a->g_nll, a->g_z,
+                       a->g_mu0, a->g_lv0, a->g_flow_lv, a->g_post_lv, a->B, a->G, a->n2, a->pw, a->gw, a->ew, nb);
+  }
   return (int)hipGetLastError();
 }

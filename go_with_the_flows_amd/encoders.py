@@ -10,7 +10,7 @@ layer-at-a-time HIP pipeline of csrc/gwtf_encoder_train.hip, forward and backwar
 plain library GEMMs and batch-norms on the HIP device (torch.matmul -> rocBLAS, F.batch_norm -> MIOpen, differentiated by
 autograd): eval mode with a gradient required, ``forward`` (the full (B,C,N) feature map) in train mode, width lists
 without kernels, an input that itself requires a gradient.  CPU tensors raise: there is no CPU path.  The per-shape heads
-(FeatureEncoder, WeightsEncoder) run one HIP launch per layer, forward and backward (csrc/gwtf_heads.hip, ``_HeadLayerFn``), for any
+(FeatureEncoder, WeightsEncoder) run one HIP launch per layer, forward and backward (csrc/gwtf_heads.hip, ``_HeadsFn``), for any
 number of rows (the gathered rows of a large data-parallel batch are walked 64 / 128 at a time inside the kernels).
 """
 import ctypes
@@ -282,103 +282,75 @@ class PointNetCloudEncoder(nn.Module):
         return self._fused(input, False, True)[1]
 
 
-class _HeadLayerFn(torch.autograd.Function):
-    """One layer of a per-shape head on the HIP device (csrc/gwtf_heads.hip): out = act(BatchNorm(x W^T + bias)), forward and
-    backward one C call each.  bn: the BatchNorm module whose buffers the forward updates (None: no BatchNorm);
-    bn_mode 0 none / 1 batch statistics / 2 running statistics; act 0 none / 1 swish / 2 log_softmax."""
+class _HeadsFn(torch.autograd.Function):
+    """One layer of a per-shape head, or two layers on the same input (the mu and logvar heads of a FeatureEncoder), on the HIP
+    device (csrc/gwtf_heads.hip): out = act(BatchNorm(x W^T + bias)) per head, forward and backward one C call each on one record
+    (include/gwtf.h GwtfHeadArgs).  specs: per head (bn, bn_mode, act) -- bn: the BatchNorm module whose buffers the forward updates
+    (None: no BatchNorm); bn_mode 0 none / 1 batch statistics / 2 running statistics; act 0 none / 1 swish / 2 log_softmax.
+    params: per head W, bias, gamma, beta (each but W may be None).  Returns the tuple of the heads' outputs."""
 
     @staticmethod
-    def forward(ctx, x, W, bias, gamma, beta, bn, bn_mode, bn_updates, act):
-        L = _lib.lib()
-        x, W = x.contiguous(), W.contiguous()
+    def forward(ctx, x, bn_updates, specs, *params):
+        x = x.contiguous()
+        params = [None if t is None else t.contiguous() for t in params]
         B, Din = x.shape
-        Dout = W.shape[0]
-        dev = x.device
-        ypre = torch.empty(B, Dout, device=dev, dtype=torch.float32)
-        out = torch.empty(B, Dout, device=dev, dtype=torch.float32)
-        stats = torch.empty(3, Dout, device=dev, dtype=torch.float32) if bn_mode else None
-        P = lambda t: None if t is None else _ptr(t.contiguous() if not t.is_contiguous() else t, 'head operand')
-        tracked = bn is not None and bn.track_running_stats and bn.running_mean is not None
-        rm, rv = (bn.running_mean, bn.running_var) if tracked else (None, None)
-        nbt = bn.num_batches_tracked.data_ptr() if (tracked and bn.num_batches_tracked is not None) else None
-        with torch.cuda.device(dev):
-            check(L.gwtf_head_layer_forward(P(x), P(W), P(bias), P(gamma), P(beta), P(rm), P(rv), nbt,
-                                            float(bn.momentum) if bn is not None and bn.momentum is not None else 0.0,
-                                            float(bn.eps) if bn is not None else 1e-5, bn_mode, int(bn_updates), act, P(ypre), P(stats),
-                                            P(out), B, Din, Dout, _stream(x)))
-        if bn_mode == 1 and tracked:
-            torch._C._increment_version([t for t in (rm, rv, bn.num_batches_tracked) if t is not None])   # written through raw pointers
-        ctx.save_for_backward(x, W, bias, gamma, beta, ypre, stats, out)
-        ctx.meta = (bn_mode, act)
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        L = _lib.lib()
-        x, W, bias, gamma, beta, ypre, stats, out = ctx.saved_tensors
-        bn_mode, act = ctx.meta
-        B, Din = x.shape
-        Dout = W.shape[0]
-        dev = x.device
-        new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
-        g_out = g_out.contiguous().float()
-        need = ctx.needs_input_grad
-        g_y = new(B, Dout)
-        g_x = new(B, Din) if need[0] else None
-        g_W = new(Dout, Din) if need[1] else None
-        g_b = new(Dout) if (bias is not None and need[2]) else None
-        g_ga = new(Dout) if (gamma is not None and need[3]) else None
-        g_be = new(Dout) if (beta is not None and need[4]) else None
-        P = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(dev):
-            check(L.gwtf_head_layer_backward(P(x), P(W), P(bias), P(gamma), P(beta), P(ypre), P(stats), P(out), P(g_out), bn_mode, act,
-                                             P(g_y), P(g_x), 0, P(g_W), P(g_b), P(g_ga), P(g_be), B, Din, Dout, _stream(x)))
-        return g_x, g_W, g_b, g_ga, g_be, None, None, None, None
-
-
-class _HeadPairFn(torch.autograd.Function):
-    """The mu and logvar heads of a FeatureEncoder (two plain Linear layers on the same hidden activations) in ONE launch forward and
-    two backward (csrc/gwtf_heads.hip head_*_pair_kernel): the same arithmetic as two _HeadLayerFn calls."""
-
-    @staticmethod
-    def forward(ctx, x, Wa, ba, Wb, bb):
-        L = _lib.lib()
-        x, Wa, Wb = x.contiguous(), Wa.contiguous(), Wb.contiguous()
-        B, Din = x.shape
-        Da, Db = Wa.shape[0], Wb.shape[0]
         new = lambda *shape: torch.empty(*shape, device=x.device, dtype=torch.float32)
-        ypre_a, out_a, ypre_b, out_b = new(B, Da), new(B, Da), new(B, Db), new(B, Db)
-        P = lambda t: None if t is None else _ptr(t.contiguous() if not t.is_contiguous() else t, 'head operand')
+        a = _lib.HeadArgs(n_heads=len(specs), B=B, Din=Din, bn_updates=int(bn_updates), stream=_stream(x))
+        buf = dict(x=x, W=params[0::4], bias=params[1::4], gamma=params[2::4], beta=params[3::4], running_mean=[], running_var=[],
+                   num_batches_tracked=[], ypre=[], stats=[], out=[])
+        written = []                                            # BatchNorm buffers the kernel updates through raw pointers
+        for h, (bn, bn_mode, act) in enumerate(specs):
+            Dout = buf['W'][h].shape[0]
+            tracked = bn is not None and bn.track_running_stats and bn.running_mean is not None
+            state = (bn.running_mean, bn.running_var, bn.num_batches_tracked) if tracked else (None, None, None)
+            for name, t in zip(('running_mean', 'running_var', 'num_batches_tracked'), state):
+                buf[name].append(t)
+            if bn_mode == 1:
+                written += [t for t in state if t is not None]
+            buf['ypre'].append(new(B, Dout))
+            buf['stats'].append(new(3, Dout) if bn_mode else None)
+            buf['out'].append(new(B, Dout))
+            a.Dout[h], a.bn_mode[h], a.act[h] = Dout, bn_mode, act
+            a.momentum[h] = float(bn.momentum) if bn is not None and bn.momentum is not None else 0.0
+            a.bn_eps[h] = float(bn.eps) if bn is not None else 1e-5
+        for given in (x, *params, *buf['running_mean'], *buf['running_var']):
+            _ptr(given, 'head operand')                          # device / dtype / layout checks of what the caller handed in
+        a.bind(buf)
         with torch.cuda.device(x.device):
-            check(L.gwtf_head_pair_forward(P(x), P(Wa), P(ba), P(Wb), P(bb), P(ypre_a), P(out_a), P(ypre_b), P(out_b), B, Din, Da, Db,
-                                           _stream(x)))
-        ctx.save_for_backward(x, Wa, ba, Wb, bb, ypre_a, out_a, ypre_b, out_b)
+            check(_lib.lib().gwtf_heads_forward(ctypes.addressof(a)))
+        if written:
+            torch._C._increment_version(written)
+        # the record stays on ctx; the tensors behind its pointers go through save_for_backward (out -> grad_fn -> ctx -> out would be a
+        # cycle that only the garbage collector frees)
+        ctx.save_for_backward(x, *params, *buf['ypre'], *buf['stats'], *buf['out'])
+        ctx.rec = a
         ctx.set_materialize_grads(False)       # an output the loss does not read arrives as None: its head's parameters get no gradient
-        return out_a, out_b
+        return tuple(buf['out'])
 
     @staticmethod
-    def backward(ctx, g_a, g_b):
-        L = _lib.lib()
-        x, Wa, ba, Wb, bb, ypre_a, out_a, ypre_b, out_b = ctx.saved_tensors
-        B, Din = x.shape
-        Da, Db = Wa.shape[0], Wb.shape[0]
+    def backward(ctx, *g_outs):
+        a = ctx.rec
+        n = a.n_heads
+        if all(g is None for g in g_outs):
+            return (None,) * (3 + 4 * n)
+        x, *saved = ctx.saved_tensors
+        params, outs = saved[:4 * n], saved[6 * n:]
         new = lambda *shape: torch.empty(*shape, device=x.device, dtype=torch.float32)
-        if g_a is None and g_b is None:
-            return None, None, None, None, None
-        used_a, used_b = g_a is not None, g_b is not None
-        g_a = torch.zeros_like(out_a) if g_a is None else g_a.contiguous().float()
-        g_b = torch.zeros_like(out_b) if g_b is None else g_b.contiguous().float()
         need = ctx.needs_input_grad
-        g_x = new(B, Din) if need[0] else None
-        g_Wa, g_Wb = (new(Da, Din) if need[1] else None), (new(Db, Din) if need[3] else None)
-        g_ba = new(Da) if (ba is not None and need[2]) else None
-        g_bb = new(Db) if (bb is not None and need[4]) else None
-        g_ya, g_yb = new(B, Da), new(B, Db)
-        P = lambda t: None if t is None else t.data_ptr()
+        used = [g is not None for g in g_outs]
+        g_out = [g.contiguous().float() if u else torch.zeros_like(o) for g, u, o in zip(g_outs, used, outs)]
+        grads = []                                               # per head: g_W, g_bias, g_gamma, g_beta
+        for h in range(n):
+            Dout = a.Dout[h]
+            grads.append(new(Dout, a.Din) if need[3 + 4 * h] else None)
+            grads += [new(Dout) if (params[4 * h + i] is not None and need[3 + 4 * h + i]) else None for i in (1, 2, 3)]
+        buf = dict(g_out=g_out, g_y=[new(a.B, a.Dout[h]) for h in range(n)], g_x=new(a.B, a.Din) if need[0] else None,
+                   g_W=grads[0::4], g_bias=grads[1::4], g_gamma=grads[2::4], g_beta=grads[3::4])
+        a.bind(buf)
+        a.stream = _stream(x)
         with torch.cuda.device(x.device):
-            check(L.gwtf_head_pair_backward(P(x), P(Wa), P(ba), P(Wb), P(bb), P(ypre_a), P(out_a), P(ypre_b), P(out_b), P(g_a), P(g_b),
-                                            P(g_ya), P(g_yb), P(g_x), P(g_Wa), P(g_ba), P(g_Wb), P(g_bb), B, Din, Da, Db, _stream(x)))
-        return g_x, (g_Wa if used_a else None), (g_ba if used_a else None), (g_Wb if used_b else None), (g_bb if used_b else None)
+            check(_lib.lib().gwtf_heads_backward(ctypes.addressof(a)))
+        return (buf['g_x'], None, None, *[g if used[i // 4] else None for i, g in enumerate(grads)])
 
 
 class FeatureEncoder(nn.Module):
@@ -446,30 +418,31 @@ class FeatureEncoder(nn.Module):
                 h = mod(h)
         return h
 
+    def _takes(self, h, lin, act):
+        """csrc/gwtf_heads.hip takes the layer `lin` -> [BatchNorm] -> activation code `act` on the rows h: fp32 rows on the HIP device
+        (any number of them: the kernels walk the batch in blocks), fp32 weights no wider than hip_max_width, sizes the kernels cover."""
+        return (h.is_cuda and h.dim() == 2 and h.dtype == torch.float32 and h.shape[0] >= 1 and lin.weight.dtype == torch.float32
+                and max(lin.weight.shape) <= self.hip_max_width
+                and bool(_lib.lib().gwtf_head_layer_supported(h.shape[0], lin.weight.shape[1], lin.weight.shape[0], act)))
+
     def _hip_layers(self, input):
-        """[(Linear, BatchNorm or None)] of the trunk when csrc/gwtf_heads.hip covers this call (fp32 rows on the HIP device -- any
-        number of them: the kernels walk the batch in blocks --, plain Linear -> [BatchNorm1d with a momentum] -> Swish layers), else
-        None: the library modules then run -- on the CPU (host-logic tests), for other dtypes."""
-        if not (input.is_cuda and input.dim() == 2 and input.dtype == torch.float32 and input.shape[0] >= 1):
-            return None
+        """[(Linear, BatchNorm or None)] of the trunk when csrc/gwtf_heads.hip covers this call (_takes for every trunk layer and head,
+        plain Linear -> [BatchNorm1d with a momentum] -> Swish layers), else None: the library modules then run -- on the CPU
+        (host-logic tests), for other dtypes."""
         layers, mods = [], list(self.features) if self.n_layers > 0 else []
         i = 0
         while i < len(mods):
             lin = mods[i]
             bn = mods[i + 1] if (i + 1 < len(mods) and isinstance(mods[i + 1], nn.modules.batchnorm._BatchNorm)) else None
             sw = mods[i + (2 if bn is not None else 1)] if i + (2 if bn is not None else 1) < len(mods) else None
-            if not (isinstance(lin, nn.Linear) and lin.bias is None and isinstance(sw, Swish) and lin.weight.dtype == torch.float32):
+            if not (isinstance(lin, nn.Linear) and lin.bias is None and isinstance(sw, Swish)):
                 return None
             if bn is not None and (bn.momentum is None or (bn.training and input.shape[0] < 2)):
                 return None
             layers.append((lin, bn))
             i += 3 if bn is not None else 2
-        if any(max(l.weight.shape) > self.hip_max_width for l, _ in layers):
-            return None
-        ok = _lib.lib().gwtf_head_layer_supported
-        dims = [(l.weight.shape[1], l.weight.shape[0], 1) for l, _ in layers] + \
-               [(m[-1].weight.shape[1], m[-1].weight.shape[0], self._head_act) for m in ([self.mus] if self.deterministic else [self.mus, self.logvars])]
-        if not all(ok(input.shape[0], din, dout, act) for din, dout, act in dims):
+        heads = [self.mus[-1]] if self.deterministic else [self.mus[-1], self.logvars[-1]]
+        if not all(self._takes(input, lin, act) for lin, act in [(l, 1) for l, _ in layers] + [(l, self._head_act) for l in heads]):
             return None
         return layers
 
@@ -498,8 +471,8 @@ class FeatureEncoder(nn.Module):
             h = input
             for lin, bn in layers:
                 mode = 0 if bn is None else (1 if (bn.training or not bn.track_running_stats) else 2)
-                h = _HeadLayerFn.apply(h, lin.weight, None, bn.weight if bn is not None else None, bn.bias if bn is not None else None,
-                                       bn, mode, bn_updates, 1)
+                h, = _HeadsFn.apply(h, bn_updates, ((bn, mode, 1),), lin.weight, None, bn.weight if bn is not None else None,
+                                    bn.bias if bn is not None else None)
         elif not sync and bn_updates == 1:
             h = self.features(input)
         else:
@@ -508,9 +481,8 @@ class FeatureEncoder(nn.Module):
 
     def _head(self, seq, h, act=0):
         lin = seq[-1]
-        if h.is_cuda and h.dtype == torch.float32 and len(seq) == 1 and lin.weight.dtype == torch.float32 and \
-                max(lin.weight.shape) <= self.hip_max_width and _lib.lib().gwtf_head_layer_supported(h.shape[0], lin.weight.shape[1], lin.weight.shape[0], act):
-            return _HeadLayerFn.apply(h, lin.weight, lin.bias, None, None, None, 0, 1, act)
+        if len(seq) == 1 and self._takes(h, lin, act):
+            return _HeadsFn.apply(h, 1, ((None, 0, act),), lin.weight, lin.bias, None, None)[0]
         out = seq(h)
         return nn.functional.log_softmax(out, dim=1) if act == 2 else out
 
@@ -519,12 +491,10 @@ class FeatureEncoder(nn.Module):
         if self.deterministic:
             return self._head(self.mus, h, self._head_act)
         la, lb = self.mus[-1], self.logvars[-1]
-        if (self._head_act == 0 and h.is_cuda and h.dtype == torch.float32 and len(self.mus) == 1 and len(self.logvars) == 1
-                and la.weight.dtype == torch.float32 and lb.weight.dtype == torch.float32
-                and max(*la.weight.shape, *lb.weight.shape) <= self.hip_max_width and os.environ.get('GWTF_NO_HEAD_PAIR') != '1'
-                and _lib.lib().gwtf_head_layer_supported(h.shape[0], la.weight.shape[1], la.weight.shape[0], 0)
-                and _lib.lib().gwtf_head_layer_supported(h.shape[0], lb.weight.shape[1], lb.weight.shape[0], 0)):
-            return _HeadPairFn.apply(h, la.weight, la.bias, lb.weight, lb.bias)      # both heads: one launch
+        if (self._head_act == 0 and len(self.mus) == 1 and len(self.logvars) == 1 and os.environ.get('GWTF_NO_HEAD_PAIR') != '1'
+                and self._takes(h, la, 0) and self._takes(h, lb, 0)):
+            # both heads: one launch (GWTF_NO_HEAD_PAIR=1: two one-head launches)
+            return _HeadsFn.apply(h, 1, ((None, 0, 0), (None, 0, 0)), la.weight, la.bias, None, None, lb.weight, lb.bias, None, None)
         return self._head(self.mus, h, self._head_act), self._head(self.logvars, h)
 
 

@@ -10,6 +10,7 @@ library launches of the module-by-module evaluation; the per-module ``forward`` 
 (used on their own and on the CPU by the host-logic tests) stays a chain of torch ops with
 the two shipped warp patterns applied as strided slices instead of the reference's index gathers.
 """
+import ctypes
 import os
 from collections import OrderedDict
 
@@ -325,82 +326,77 @@ class _PriorFlowFn(torch.autograd.Function):
         return g_g, g_raw, None, None, None, None, None
 
 
+def _latent_args(rows, cfg, **tensors):
+    """The record of one latent-loss launch (include/gwtf.h GwtfLatentLossArgs) on the current stream of z's device."""
+    from . import _lib
+    B, G, n2, pw, gw, ew = cfg
+    a = _lib.LatentLossArgs(B=B, G=G, n2=n2, rows=rows, pw=pw, gw=gw, ew=ew, stream=_lib._stream(tensors['z']))
+    for name, t in tensors.items():
+        _lib._ptr(t, name)                       # device / dtype / layout checks
+    a.bind(tensors)
+    return a
+
+
+def _latent_forward(ctx, rows, nll, z, mu0, lv0, flow_lv, post_lv, pw, gw, ew):
+    """forward of LatentLossFn (rows = 0: mu0, lv0 (G,)) and LatentLossRowsFn (rows = 1: (B, G))."""
+    from . import _lib
+    B, G = z.shape if z.dim() == 2 else (-1, -1)
+    n2 = flow_lv.shape[0] if flow_lv.dim() == 3 else -1
+    base, what, base_s = ((B, G), ' (per-row base)', '(B,G)') if rows else ((G,), '', '(G,)')
+    if (min(B, G, n2) < 1 or nll.shape != (B,) or mu0.shape != base or lv0.shape != base or flow_lv.shape != (n2, B, G)
+            or post_lv.shape != (B, G)):
+        raise _lib.GwtfError(f'latent loss{what}: shapes {tuple(nll.shape)} {tuple(z.shape)} {tuple(mu0.shape)} '
+                             f'{tuple(lv0.shape)} {tuple(flow_lv.shape)} {tuple(post_lv.shape)} are not (B,), (B,G), {base_s}, {base_s}, '
+                             f'(n2,B,G), (B,G)')
+    ws = _lib.lib().gwtf_latent_loss_workspace_floats(B, G)
+    buf = torch.empty(ws + 4, device=z.device, dtype=torch.float32)
+    out = buf[ws:]
+    cfg = (B, G, n2, pw, gw, ew)
+    a = _latent_args(rows, cfg, nll=nll, z=z, mu0=mu0, lv0=lv0, flow_lv=flow_lv, post_lv=post_lv, workspace=buf, out4=out)
+    _lib.check(_lib.lib().gwtf_latent_loss_forward(ctypes.addressof(a)))
+    ctx.save_for_backward(z, mu0, lv0)
+    ctx.cfg = cfg
+    return out
+
+
+def _latent_backward(ctx, rows, g_out):
+    from . import _lib
+    z, mu0, lv0 = ctx.saved_tensors
+    B, G, n2 = ctx.cfg[:3]
+    g_out = g_out.contiguous()
+    nb = mu0.numel()                             # G, or B * G with one base Gaussian per row
+    buf = torch.empty(B + (n2 + 2) * B * G + 2 * nb, device=z.device, dtype=torch.float32)
+    g_nll, g_z, g_post, g_flow, g_mu0, g_lv0 = buf.split([B, B * G, B * G, n2 * B * G, nb, nb])
+    a = _latent_args(rows, ctx.cfg, g_out4=g_out, z=z, mu0=mu0, lv0=lv0, g_nll=g_nll, g_z=g_z, g_mu0=g_mu0,
+                     g_lv0=g_lv0, g_flow_lv=g_flow, g_post_lv=g_post)
+    _lib.check(_lib.lib().gwtf_latent_loss_backward(ctypes.addressof(a)))
+    return (g_nll, g_z.view(B, G), g_mu0.view_as(mu0), g_lv0.view_as(lv0), g_flow.view(n2, B, G), g_post.view(B, G), None, None, None)
+
+
 class LatentLossFn(torch.autograd.Function):
     """(loss, pnll, gnll, gent) of Flow_Mixture_Loss (reference losses.py:159-170) from the per-shape point NLL and the prior's
-    tensors: one HIP launch forward, one backward (csrc/gwtf_latent.hip) in place of ~55 elementwise / reduction launches."""
+    tensors: two HIP launches forward, one backward (csrc/gwtf_latent.hip) in place of ~55 elementwise / reduction launches."""
 
     @staticmethod
     def forward(ctx, nll, z, mu0, lv0, flow_lv, post_lv, pw, gw, ew):
-        from . import _lib
-        B, G = z.shape
-        n2 = flow_lv.shape[0]
-        if nll.shape != (B,) or mu0.shape != (G,) or lv0.shape != (G,) or flow_lv.shape != (n2, B, G) or post_lv.shape != (B, G):
-            raise _lib.GwtfError(f'latent loss: shapes {tuple(nll.shape)} {tuple(z.shape)} {tuple(mu0.shape)} {tuple(lv0.shape)} '
-                                 f'{tuple(flow_lv.shape)} {tuple(post_lv.shape)} are not (B,), (B,G), (G,), (G,), (n2,B,G), (B,G)')
-        L, P = _lib.lib(), _lib._ptr
-        ws = L.gwtf_latent_loss_workspace_floats(B, G)
-        buf = torch.empty(ws + 4, device=z.device, dtype=torch.float32)
-        out = buf[ws:]
-        _lib.check(L.gwtf_latent_loss_forward(P(nll, 'nll'), P(z, 'z'), P(mu0, 'mu0'), P(lv0, 'lv0'), P(flow_lv, 'flow_lv'),
-                                              P(post_lv, 'post_lv'), buf.data_ptr(), out.data_ptr(), B, G, n2, pw, gw, ew,
-                                              _lib._stream(z)))
-        ctx.save_for_backward(z, mu0, lv0)
-        ctx.cfg = (B, G, n2, pw, gw, ew)
-        return out
+        return _latent_forward(ctx, 0, nll, z, mu0, lv0, flow_lv, post_lv, pw, gw, ew)
 
     @staticmethod
     def backward(ctx, g_out):
-        from . import _lib
-        z, mu0, lv0 = ctx.saved_tensors
-        B, G, n2, pw, gw, ew = ctx.cfg
-        g_out = g_out.contiguous()
-        buf = torch.empty(B + (n2 + 2) * B * G + 2 * G, device=z.device, dtype=torch.float32)
-        g_nll, g_z, g_post, g_flow, g_mu0, g_lv0 = buf.split([B, B * G, B * G, n2 * B * G, G, G])
-        _lib.check(_lib.lib().gwtf_latent_loss_backward(_lib._ptr(g_out, 'g_out'), z.data_ptr(), mu0.data_ptr(), lv0.data_ptr(),
-                                                        g_nll.data_ptr(), g_z.data_ptr(), g_mu0.data_ptr(), g_lv0.data_ptr(),
-                                                        g_flow.data_ptr(), g_post.data_ptr(), B, G, n2, pw, gw, ew, _lib._stream(z)))
-        return g_nll, g_z.view(B, G), g_mu0, g_lv0, g_flow.view(n2, B, G), g_post.view(B, G), None, None, None
+        return _latent_backward(ctx, 0, g_out)
 
 
 class LatentLossRowsFn(torch.autograd.Function):
     """LatentLossFn with one base Gaussian PER ROW: mu0, lv0 (B, G) -- the single-view reconstruction model's
-    g0_prior(img_encoder(images)).  Same four values, one HIP launch forward and one (elementwise) backward."""
+    g0_prior(img_encoder(images)).  Same four values, the same launches forward and one (elementwise) backward."""
 
     @staticmethod
     def forward(ctx, nll, z, mu0, lv0, flow_lv, post_lv, pw, gw, ew):
-        from . import _lib
-        B, G = z.shape if z.dim() == 2 else (-1, -1)
-        n2 = flow_lv.shape[0] if flow_lv.dim() == 3 else -1
-        if (min(B, G, n2) < 1 or nll.shape != (B,) or mu0.shape != (B, G) or lv0.shape != (B, G) or flow_lv.shape != (n2, B, G)
-                or post_lv.shape != (B, G)):
-            raise _lib.GwtfError(f'latent loss (per-row base): shapes {tuple(nll.shape)} {tuple(z.shape)} {tuple(mu0.shape)} '
-                                 f'{tuple(lv0.shape)} {tuple(flow_lv.shape)} {tuple(post_lv.shape)} are not (B,), (B,G), (B,G), (B,G), '
-                                 f'(n2,B,G), (B,G)')
-        L, P = _lib.lib(), _lib._ptr
-        ws = L.gwtf_latent_loss_workspace_floats(B, G)
-        buf = torch.empty(ws + 4, device=z.device, dtype=torch.float32)
-        out = buf[ws:]
-        _lib.check(L.gwtf_latent_loss_rows_forward(P(nll, 'nll'), P(z, 'z'), P(mu0, 'mu0'), P(lv0, 'lv0'), P(flow_lv, 'flow_lv'),
-                                                   P(post_lv, 'post_lv'), buf.data_ptr(), out.data_ptr(), B, G, n2, pw, gw, ew,
-                                                   _lib._stream(z)))
-        ctx.save_for_backward(z, mu0, lv0)
-        ctx.cfg = (B, G, n2, pw, gw, ew)
-        return out
+        return _latent_forward(ctx, 1, nll, z, mu0, lv0, flow_lv, post_lv, pw, gw, ew)
 
     @staticmethod
     def backward(ctx, g_out):
-        from . import _lib
-        z, mu0, lv0 = ctx.saved_tensors
-        B, G, n2, pw, gw, ew = ctx.cfg
-        g_out = g_out.contiguous()
-        buf = torch.empty(B + (n2 + 4) * B * G, device=z.device, dtype=torch.float32)
-        g_nll, g_z, g_post, g_mu0, g_lv0, g_flow = buf.split([B, B * G, B * G, B * G, B * G, n2 * B * G])
-        _lib.check(_lib.lib().gwtf_latent_loss_rows_backward(_lib._ptr(g_out, 'g_out'), z.data_ptr(), mu0.data_ptr(), lv0.data_ptr(),
-                                                             g_nll.data_ptr(), g_z.data_ptr(), g_mu0.data_ptr(), g_lv0.data_ptr(),
-                                                             g_flow.data_ptr(), g_post.data_ptr(), B, G, n2, pw, gw, ew,
-                                                             _lib._stream(z)))
-        return (g_nll, g_z.view(B, G), g_mu0.view(B, G), g_lv0.view(B, G), g_flow.view(n2, B, G), g_post.view(B, G), None, None,
-                None)
+        return _latent_backward(ctx, 1, g_out)
 
 
 class GaussianFlowNLL(nn.Module):

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define GWTF_ABI_VERSION 11
+#define GWTF_ABI_VERSION 12
 #define GWTF_E_BADARG 10001   /* shape / mode / width outside what the kernels support */
 #define GWTF_E_UNSUPPORTED 10002   /* a layer-width list no kernel instantiation was built for */
 #define GWTF_E_FEW_VALUES 10003   /* batch statistics over fewer than 2 values per channel */
@@ -133,26 +133,38 @@ int gwtf_pack_weights_exact(const float* raw, const float* packed_film /*eval pa
                             float* packed_x, int K, int Cper, int f, int G, int pattern0, void* stream);
 int gwtf_stack_forward_exact(const GwtfStackArgs* args, int rerun);
 /* Latent-space loss terms of the training step and their combination with the point NLL (reference lib/networks/losses.py:24-33
- * GaussianFlowNLL, :36-41 GaussianEntropy, :159-170 Flow_Mixture_Loss.forward), one launch each way (csrc/gwtf_latent.hip):
- *   nll [B] per-shape point NLL (gwtf_mixture_nll); z [B][G] = g_prior_samples[0]; mu0, lv0 [G] = the base Gaussian of the prior flow;
- *   flow_lv [n2][B][G] = the prior flow's stacked logvars (g_prior_logvars[1:]); post_lv [B][G] = g_posterior_logvars
- *   workspace: gwtf_latent_loss_workspace_floats(B, G) floats.  out4 = {loss = pw pnll + gw gnll - ew gent, pnll, gnll, gent}.   backward: g_out4 = upstream of the four outputs. */
-int gwtf_latent_loss_workspace_floats(int B, int G);       /* device scratch of the forward (block partials; 8-byte aligned) */
-int gwtf_latent_loss_forward(const float* nll, const float* z, const float* mu0, const float* lv0, const float* flow_lv,
-                             const float* post_lv, float* workspace, float* out4, int B, int G, int n2, float pw, float gw, float ew,
-                             void* stream);
-int gwtf_latent_loss_backward(const float* g_out4, const float* z, const float* mu0, const float* lv0, float* g_nll, float* g_z,
-                              float* g_mu0, float* g_lv0, float* g_flow_lv, float* g_post_lv, int B, int G, int n2, float pw, float gw,
-                              float ew, void* stream);
-/* The same four values with ONE BASE GAUSSIAN PER ROW: mu0, lv0 [B][G] (single-view reconstruction: g0_prior(img_encoder(images))), and
- * g_mu0, g_lv0 [B][G] in the backward, which is elementwise throughout.  Every other argument, the workspace size
- * (gwtf_latent_loss_workspace_floats) and the two-stage block-ordered reduction (no float atomics: same inputs, same bits) as above. */
-int gwtf_latent_loss_rows_forward(const float* nll, const float* z, const float* mu0, const float* lv0, const float* flow_lv,
-                                  const float* post_lv, float* workspace, float* out4, int B, int G, int n2, float pw, float gw,
-                                  float ew, void* stream);
-int gwtf_latent_loss_rows_backward(const float* g_out4, const float* z, const float* mu0, const float* lv0, float* g_nll, float* g_z,
-                                   float* g_mu0, float* g_lv0, float* g_flow_lv, float* g_post_lv, int B, int G, int n2, float pw,
-                                   float gw, float ew, void* stream);
+ * GaussianFlowNLL, :36-41 GaussianEntropy, :159-170 Flow_Mixture_Loss.forward), two launches forward and one backward
+ * (csrc/gwtf_latent.hip).  The base Gaussian of the prior flow is shared by the batch (rows = 0: mu0, lv0 and their gradients [G], the
+ * generative / autoencoding models' learned parameters) or there is one per row (rows = 1: [B][G], single-view reconstruction:
+ * g0_prior(img_encoder(images)); its backward is elementwise throughout).  The forward is a two-stage block-ordered reduction (no
+ * float atomics: same inputs, same bits). */
+typedef struct GwtfLatentLossArgs {
+  const float* nll;                  /* [B] per-shape point NLL (gwtf_mixture_nll) */
+  const float* z;                    /* [B][G] = g_prior_samples[0] */
+  const float* mu0;                  /* [G] (rows = 0) or [B][G] (rows = 1) */
+  const float* lv0;                  /* as mu0 */
+  const float* flow_lv;              /* [n2][B][G] = the prior flow's stacked logvars (g_prior_logvars[1:]) */
+  const float* post_lv;              /* [B][G] = g_posterior_logvars */
+  float* workspace;                  /* forward: gwtf_latent_loss_workspace_floats(B, G) floats (block partials; 8-byte aligned) */
+  float* out4;                       /* forward: {loss = pw pnll + gw gnll - ew gent, pnll, gnll, gent} */
+  const float* g_out4;               /* backward: upstream of the four outputs */
+  float* g_nll;                      /* backward outputs, each of the shape of its forward operand */
+  float* g_z;
+  float* g_mu0;
+  float* g_lv0;
+  float* g_flow_lv;
+  float* g_post_lv;
+  int B, G, n2;
+  int rows;                          /* 0: one base Gaussian for the batch, 1: one per row */
+  float pw, gw, ew;
+  void* stream;
+} GwtfLatentLossArgs;
+/* Both validate on the host before any launch.  GWTF_E_BADARG: a NULL record, a NULL pointer among those the direction uses
+ * (forward: nll .. out4; backward: g_out4, z, mu0, lv0 and the six outputs), B, G or n2 < 1, rows outside 0..1, B * G beyond the
+ * kernels' int element index.  gwtf_latent_loss_workspace_floats returns 0 for sizes the launches refuse. */
+int gwtf_latent_loss_workspace_floats(int B, int G);
+int gwtf_latent_loss_forward(const GwtfLatentLossArgs* args);
+int gwtf_latent_loss_backward(const GwtfLatentLossArgs* args);
 /* Tile plan of a forward launch (what stack_dispatch decides; diagnostic + tests): out[0] = points per wavefront of the main
  * launch, out[1] = its workgroups, out[2] = points per wavefront of the tail launch (0: none), out[3] = its workgroups.
  * The choice minimises resident rounds x the cost of a round of that tile (calibrated, csrc/gwtf_stack.hip tile_cost). */
@@ -517,35 +529,51 @@ int gwtf_prior_backward(const float* g, const float* raw, const float* gs, const
 
 /* Per-shape MLP heads: FeatureEncoder / WeightsEncoder (lib/networks/encoders.py:31-89) = n_layers x [Linear(no bias) ->
  * BatchNorm1d -> Swish], then Linear(bias) heads (mu, logvar), the mixture-weight head ending in log_softmax (:87-91) -- the
- * modules g_posterior, p_prior and mixture_weights_encoder of the model (models.py:51-59, flow_mixture.py:28-32).  ONE LAYER per
- * call, forward and backward; a workgroup owns 16 output columns and all B <= 128 rows, so BatchNorm's column statistics are local.
+ * modules g_posterior, p_prior and mixture_weights_encoder of the model (models.py:51-59, flow_mixture.py:28-32).  One launch runs
+ * `n_heads` (1 or 2) LAYERS ON THE SAME INPUT x, forward and backward: one layer of a trunk, or the mu and logvar heads of a
+ * FeatureEncoder (encoders.py:55-60) together.  A workgroup owns 16 output columns of one head and all B rows, so BatchNorm's column
+ * statistics are local; the workgroups of head 0 come first, then head 1's.  Per-head fields are arrays of two (entry 1 is not read
+ * when n_heads = 1).
  *   x [B][Din], W [Dout][Din], bias / gamma / beta [Dout] (each may be NULL), out [B][Dout]
  *   bn_mode  0: no BatchNorm   1: batch statistics; running_mean / running_var (may be NULL) get the momentum update with the
  *            unbiased batch variance applied `bn_updates` times, *num_batches_tracked += bn_updates   2: running statistics
  *   act      0: none   1: swish   2: log_softmax over the columns (Dout <= 16)
  *   ypre [B][Dout] = x W^T (the backward's input), stats [3][Dout] = mean, biased variance, 1/sqrt(var + bn_eps) used
- * backward: g_out [B][Dout] -> g_y [B][Dout] (scratch: dL/d(x W^T)), g_x [B][Din] (NULL: not wanted; accumulate_g_x != 0: added
- *   to what is there -- two heads on one trunk), g_W [Dout][Din], g_bias / g_gamma / g_beta [Dout] (each may be NULL).
- * gwtf_head_layer_supported -> 1 when the kernels cover (B, Din, Dout, act). */
+ * backward: g_out [B][Dout] -> g_y [B][Dout] (scratch: dL/d(x W^T)), g_W [Dout][Din], g_bias / g_gamma / g_beta [Dout] (each may be
+ *   NULL), g_x [B][Din] (NULL: not wanted) = the sum of the heads' input gradients: always overwritten, head 1's product accumulates
+ *   onto head 0's inside the kernel. */
+typedef struct GwtfHeadArgs {
+  const float* x;
+  float* g_x;
+  int n_heads, B, Din;
+  int bn_updates;                    /* >= 1 */
+  const float* W[2];
+  const float* bias[2];
+  const float* gamma[2];
+  const float* beta[2];
+  float* running_mean[2];
+  float* running_var[2];
+  long long* num_batches_tracked[2]; /* may be NULL */
+  float* ypre[2];                    /* forward outputs (read by the backward) */
+  float* stats[2];                   /* NULL with bn_mode 0 */
+  float* out[2];
+  const float* g_out[2];             /* backward */
+  float* g_y[2];
+  float* g_W[2];
+  float* g_bias[2];
+  float* g_gamma[2];
+  float* g_beta[2];
+  int Dout[2], bn_mode[2], act[2];
+  float momentum[2], bn_eps[2];
+  void* stream;
+} GwtfHeadArgs;
+/* Both validate on the host before any launch.  GWTF_E_BADARG: a NULL record, n_heads outside 1..2, bn_updates < 1, a NULL x, and per
+ * head: a NULL W, ypre or out (backward also g_out or g_y), sizes gwtf_head_layer_supported refuses (B outside 1..65536, Din or Dout
+ * outside 1..4096, act 2 with Dout > 16), bn_mode or act outside 0..2, bn_mode != 0 without stats, bn_mode 2 without running
+ * statistics, bn_mode 1 with B < 2.  gwtf_head_layer_supported -> 1 when the kernels cover (B, Din, Dout, act). */
 int gwtf_head_layer_supported(int B, int Din, int Dout, int act);
-int gwtf_head_layer_forward(const float* x, const float* W, const float* bias, const float* gamma, const float* beta,
-                            float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float bn_eps,
-                            int bn_mode, int bn_updates, int act, float* ypre, float* stats, float* out, int B, int Din, int Dout,
-                            void* stream);
-int gwtf_head_layer_backward(const float* x, const float* W, const float* bias, const float* gamma, const float* beta,
-                             const float* ypre, const float* stats, const float* out, const float* g_out, int bn_mode, int act,
-                             float* g_y, float* g_x, int accumulate_g_x, float* g_W, float* g_bias, float* g_gamma, float* g_beta,
-                             int B, int Din, int Dout, void* stream);
-/* The two plain Linear heads of a FeatureEncoder (mu and logvar: y = x W^T + bias, no BatchNorm, no activation; reference
- * encoders.py:55-60) on the same input, one launch forward and two backward where two calls of gwtf_head_layer_* are two and four:
- * ypre_* / out_* [B][Dout_*] as gwtf_head_layer_forward leaves them; g_y_* [B][Dout_*] scratch; g_x [B][Din] (may be NULL) = the sum of
- * both heads' input gradients; g_W_* [Dout_*][Din], g_bias_* [Dout_*] (each may be NULL). */
-int gwtf_head_pair_forward(const float* x, const float* Wa, const float* bias_a, const float* Wb, const float* bias_b, float* ypre_a,
-                           float* out_a, float* ypre_b, float* out_b, int B, int Din, int Dout_a, int Dout_b, void* stream);
-int gwtf_head_pair_backward(const float* x, const float* Wa, const float* bias_a, const float* Wb, const float* bias_b,
-                            const float* ypre_a, const float* out_a, const float* ypre_b, const float* out_b, const float* g_out_a,
-                            const float* g_out_b, float* g_y_a, float* g_y_b, float* g_x, float* g_Wa, float* g_bias_a, float* g_Wb,
-                            float* g_bias_b, int B, int Din, int Dout_a, int Dout_b, void* stream);
+int gwtf_heads_forward(const GwtfHeadArgs* args);
+int gwtf_heads_backward(const GwtfHeadArgs* args);
 
 /* Image encoder of the single-view-reconstruction model (go_with_the_flows_amd/resnet.py): the 4-channel ResNet-18 of the
  * reference's lib/networks/resnet.py:9-224 (BasicBlock x [2,2,2,2], fc -> fc_bn -> ReLU head), EVAL-MODE forward only

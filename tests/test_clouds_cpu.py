@@ -115,7 +115,7 @@ def test_abi_additions_are_declared_bound_and_check_their_arguments():
     declared = set(re.findall(r'\b(gwtf_[a-z0-9_]+)\s*\(', header))
     for name in ('gwtf_sample_clouds', 'gwtf_cloud_partials'):
         assert name in declared and name in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 11 and '#define GWTF_ABI_VERSION 11' in header
+    assert _lib.ABI_VERSION == 12 and '#define GWTF_ABI_VERSION 12' in header
     # the ctypes mirror follows the record field for field
     body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct GwtfCloudArgs \{(.*?)\} GwtfCloudArgs;', header, re.S).group(1), flags=re.S)
     names = []
@@ -123,7 +123,7 @@ def test_abi_additions_are_declared_bound_and_check_their_arguments():
         names += [re.search(r'(\w+)\s*(?:\[\d+\])?$', piece.strip()).group(1) for piece in decl.split(',')]
     assert names == [n for n, _ in _lib.CloudArgs._fields_]
     L = _lib.lib()
-    assert L.gwtf_abi_version() == 11
+    assert L.gwtf_abi_version() == 12
     assert L.gwtf_cloud_partials(4096) == 16 and L.gwtf_cloud_partials(257) == 2 and L.gwtf_cloud_partials(0) == 0
     assert L.gwtf_sample_clouds(None) == 10001
     fake = 0x1000                                     # never dereferenced: every check below fails before anything is launched

@@ -88,7 +88,8 @@ def test_ctypes_records_follow_the_header_field_for_field():
     header = open(os.path.join(ROOT, 'include', 'gwtf.h')).read()
     for c_name, mirror, at_least in (('GwtfStackArgs', _lib.StackArgs, 22), ('GwtfTrainCtx', _lib.TrainCtx, 43),
                                      ('GwtfEncTrainCtx', _lib.EncTrainCtx, 47), ('GwtfCloudArgs', _lib.CloudArgs, 31),
-                                     ('GwtfRouteArgs', _lib.RouteArgs, 20), ('GwtfRoutedStackArgs', _lib.RoutedStackArgs, 17)):
+                                     ('GwtfRouteArgs', _lib.RouteArgs, 20), ('GwtfRoutedStackArgs', _lib.RoutedStackArgs, 17),
+                                     ('GwtfHeadArgs', _lib.HeadArgs, 28), ('GwtfLatentLossArgs', _lib.LatentLossArgs, 23)):
         declared = _c_struct_fields(header, c_name)
         assert len(declared) >= at_least, c_name
         assert _mirror_fields(mirror) == declared, c_name
@@ -129,6 +130,62 @@ def test_encoder_train_record_is_validated_before_anything_is_launched():
     assert L.gwtf_enc_train_phase(ctypes.addressof(ok), _lib.ENC_PHASE_FWD_LAYER, 4) == E
     assert L.gwtf_enc_train_phase(ctypes.addressof(ok), _lib.ENC_PHASE_BWD_LAYER, 4) == E
     assert L.gwtf_enc_train_phase(ctypes.addressof(ok), _lib.ENC_PHASE_BWD_LAYER, -1) == E
+
+
+def _filled(cls, *fields):
+    """byref of a record of `cls` with every pointer but the stream set (the validation never reads an address), then the given dicts
+    of fields in turn: a list sets an array field, a tuple (h, v) its entry h."""
+    t = cls()
+    for name, ctype in t._fields_:
+        if ctype is ctypes.c_void_p and name != 'stream':
+            setattr(t, name, 0x1000)
+        elif issubclass(ctype, ctypes.Array) and ctype._type_ is ctypes.c_void_p:
+            getattr(t, name)[:] = [0x1000] * ctype._length_
+    for name, value in (item for d in fields for item in d.items()):
+        if isinstance(value, tuple):
+            getattr(t, name)[value[0]] = value[1]
+        elif isinstance(value, list):
+            getattr(t, name)[:] = value
+        else:
+            setattr(t, name, value)
+    return ctypes.byref(t)                                     # (keeps the record alive for the call)
+
+
+def test_head_and_latent_loss_records_are_validated_before_anything_is_launched():
+    """gwtf_heads_forward / _backward and gwtf_latent_loss_forward / _backward refuse (GWTF_E_BADARG, host only) every record the
+    header says they refuse: one call per rule, each a valid record with one thing wrong."""
+    L = _lib.lib()
+    E = 10001
+    # two heads: batch-statistic BatchNorm + swish, and a log-softmax head
+    heads = lambda **bad: _filled(_lib.HeadArgs, dict(n_heads=2, B=4, Din=8, bn_updates=1, Dout=[5, 3], bn_mode=[1, 0], act=[1, 2]), bad)
+    both = (L.gwtf_heads_forward, L.gwtf_heads_backward)
+    for call in both:
+        assert call(None) == E
+        for bad in (dict(n_heads=0), dict(n_heads=3), dict(x=None), dict(W=(0, None)), dict(W=(1, None)), dict(ypre=(1, None)),
+                    dict(out=(0, None)),
+                    dict(B=0), dict(B=65537), dict(Din=0), dict(Din=4097), dict(Dout=(1, 0)), dict(Dout=(0, 4097)),       # dims_ok
+                    dict(bn_mode=(0, 3)), dict(bn_mode=(1, -1)), dict(act=(0, 3)), dict(act=(1, -1)),
+                    dict(stats=(0, None)),                                                    # bn_mode != 0 without stats
+                    dict(bn_mode=(1, 2), running_mean=(1, None)), dict(bn_mode=(0, 2), running_var=(0, None)),
+                    dict(Dout=(1, 17)),                                                       # act 2 wider than a column block
+                    dict(B=1),                                                                # batch statistics of one row
+                    dict(bn_updates=0)):
+            assert call(heads(**bad)) == E, bad
+    for bad in (dict(g_out=(0, None)), dict(g_out=(1, None)), dict(g_y=(0, None)), dict(g_y=(1, None))):
+        assert L.gwtf_heads_backward(heads(**bad)) == E, bad
+
+    latent = lambda **bad: _filled(_lib.LatentLossArgs, dict(B=2, G=3, n2=2, rows=0, pw=1.0, gw=1.0, ew=1.0), bad)
+    fwd_ptrs = ('nll', 'z', 'mu0', 'lv0', 'flow_lv', 'post_lv', 'workspace', 'out4')
+    bwd_ptrs = ('g_out4', 'z', 'mu0', 'lv0', 'g_nll', 'g_z', 'g_mu0', 'g_lv0', 'g_flow_lv', 'g_post_lv')
+    for call, ptrs in ((L.gwtf_latent_loss_forward, fwd_ptrs), (L.gwtf_latent_loss_backward, bwd_ptrs)):
+        assert call(None) == E
+        for rows in (0, 1):
+            for bad in [dict(B=0), dict(G=0), dict(n2=0), dict(B=-1), dict(B=1 << 20, G=1 << 12)] + [{p: None} for p in ptrs]:
+                assert call(latent(rows=rows, **bad)) == E, (rows, bad)
+        assert call(latent(rows=2)) == E and call(latent(rows=-1)) == E
+    W = L.gwtf_latent_loss_workspace_floats
+    assert W(2, 3) == 2 and W(256, 2) == 4 and W(257, 1) == 4                    # two floats per block of 256 elements
+    assert W(0, 3) == 0 and W(2, -1) == 0 and W(1 << 20, 1 << 12) == 0 and W(1 << 16, 1 << 15) == 0      # what the launches refuse
 
 
 def test_buffer_sizes_and_raw_arena_layout():

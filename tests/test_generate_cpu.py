@@ -28,11 +28,11 @@ def test_abi_additions_are_declared_bound_and_check_their_arguments():
     declared = set(re.findall(r'\b(gwtf_[a-z0-9_]+)\s*\(', header))
     for name in ('gwtf_mixture_route', 'gwtf_stack_forward_routed', 'gwtf_route_tiles'):
         assert name in declared and name in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 11 and '#define GWTF_ABI_VERSION 11' in header
+    assert _lib.ABI_VERSION == 12 and '#define GWTF_ABI_VERSION 12' in header
     assert _record_fields(header, 'GwtfRouteArgs') == [n for n, _ in _lib.RouteArgs._fields_]
     assert _record_fields(header, 'GwtfRoutedStackArgs') == [n for n, _ in _lib.RoutedStackArgs._fields_]
     L = _lib.lib()
-    assert L.gwtf_abi_version() == 11
+    assert L.gwtf_abi_version() == 12
     fake = 0x1000                                     # never dereferenced: every check below fails before anything is launched
 
     ok = dict(logits=fake, mu0=fake, lv0=fake, state=fake, thresholds=fake, tile_comp=fake, perm=fake, zp=fake, labels=fake,

@@ -2,12 +2,14 @@
 (csrc/gwtf_heads.hip: one launch per layer, forward and backward) against the GENUINE reference's outputs and gradients (golden g20:
 g_posterior, p_prior and mixture_weights_encoder at the shipped configs' sizes, train and eval BatchNorm, the reference's fp64 run with
 its own fp32 noise recorded per tensor).  Needs an MI355X."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
 
 from conftest import golden
-from go_with_the_flows_amd import encoders
+from go_with_the_flows_amd import _lib, encoders
 from go_with_the_flows_amd.synth import synth_state
 
 pytestmark = pytest.mark.gpu
@@ -105,7 +107,7 @@ def test_heads_refuse_what_the_kernels_do_not_cover_and_fall_back_to_the_library
 
 @pytest.mark.parametrize('B,din,dout', [(64, 512, 128), (64, 128, 3), (130, 40, 33)])
 def test_head_pair_launch_equals_the_two_single_launches_bit_for_bit(B, din, dout, monkeypatch):
-    """The mu / logvar heads in one launch (csrc/gwtf_heads.hip head_*_pair_kernel): same blocks, same products as one launch per head;
+    """The mu / logvar heads in one launch (csrc/gwtf_heads.hip, a GwtfHeadArgs record of two heads): same blocks, same products as one launch per head;
     also with only ONE of the two outputs in the loss (the other head's upstream gradient is None)."""
     torch.manual_seed(B + dout)
     m = encoders.FeatureEncoder(1, din, dout, deterministic=False, easy_init=True).to(DEV).train()
@@ -132,3 +134,50 @@ def test_head_pair_launch_equals_the_two_single_launches_bit_for_bit(B, din, dou
                 assert float((a - b).abs().max()) <= 2e-6 * float(b.abs().max())
             else:
                 assert (a is None and b is None) or torch.equal(a, b), i
+
+
+@pytest.mark.parametrize('B,din,dout0,dout1', [(2, 17, 5, 3), (130, 130, 33, 16)])
+def test_two_heads_of_mixed_modes_equal_two_one_head_launches(B, din, dout0, dout1):
+    """The record itself (gwtf_heads_forward / _backward through _lib), two heads of DIFFERENT kinds in one launch -- head 0
+    batch-statistic BatchNorm + swish with running statistics, head 1 a log-softmax head -- against two one-head launches of the same
+    inputs.  (2, 17, 5, 3): the smallest BatchNorm batch, ragged column blocks; (130, 130, 33, 16): rows beyond the 128-row register path,
+    Din beyond the split-K threshold of 128, head 1 starting at block 3.  Every output, buffer and parameter gradient bit for bit;
+    dL/dx (head 1's product accumulated onto head 0's inside the kernel, against the sum of two launches) within 2e-6 of its largest
+    entry, the bar of the pair test above for the same change of association."""
+    L = _lib.lib()
+    gen = torch.Generator().manual_seed(B + dout0)
+    rnd = lambda *shape: torch.randn(*shape, generator=gen).to(DEV)
+    new = lambda *shape: torch.empty(*shape, device=DEV)
+    douts, modes, acts = (dout0, dout1), (1, 0), (1, 2)
+    x = rnd(B, din)
+    given = [dict(W=rnd(d, din), bias=rnd(d), g_out=rnd(B, d)) for d in douts]
+    given[0].update(gamma=1.0 + 0.5 * rnd(dout0), beta=rnd(dout0))
+
+    def launch(heads):
+        """forward + backward of the listed heads in one record; fresh outputs and BatchNorm buffers"""
+        a = _lib.HeadArgs(n_heads=len(heads), B=B, Din=din, bn_updates=2, stream=_lib._stream(x))
+        t = dict(x=x, g_x=new(B, din))
+        for k, h in enumerate(heads):
+            d = douts[h]
+            a.Dout[k], a.bn_mode[k], a.act[k], a.momentum[k], a.bn_eps[k] = d, modes[h], acts[h], 0.1, 1e-5
+            own = dict(given[h], ypre=new(B, d), out=new(B, d), g_y=new(B, d), g_W=new(d, din), g_bias=new(d))
+            if modes[h]:
+                own.update(stats=new(3, d), running_mean=torch.zeros(d, device=DEV), running_var=torch.ones(d, device=DEV),
+                           num_batches_tracked=torch.zeros((), device=DEV, dtype=torch.int64), g_gamma=new(d), g_beta=new(d))
+            for name, v in own.items():
+                t.setdefault(name, [None] * len(heads))[k] = v
+        a.bind(t)
+        _lib.check(L.gwtf_heads_forward(ctypes.addressof(a)))
+        _lib.check(L.gwtf_heads_backward(ctypes.addressof(a)))
+        torch.cuda.synchronize()
+        return t
+
+    both, one = launch([0, 1]), [launch([0]), launch([1])]
+    for h in (0, 1):
+        names = ['out', 'ypre', 'g_y', 'g_W', 'g_bias'] + (['stats', 'running_mean', 'running_var', 'num_batches_tracked', 'g_gamma',
+                                                            'g_beta'] if modes[h] else [])
+        for name in names:
+            assert torch.equal(both[name][h], one[h][name][0]), (h, name)
+    assert int(both['num_batches_tracked'][0]) == 2
+    g_x = one[0]['g_x'] + one[1]['g_x']
+    assert float((both['g_x'] - g_x).abs().max()) <= 2e-6 * float(g_x.abs().max())

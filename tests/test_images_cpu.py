@@ -186,14 +186,14 @@ def test_abi_addition_is_declared_bound_and_checks_its_arguments():
     header = open(os.path.join(ROOT, 'include', 'gwtf.h')).read()
     declared = set(re.findall(r'\b(gwtf_[a-z0-9_]+)\s*\(', header))
     assert 'gwtf_transform_images' in declared and 'gwtf_transform_images' in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 11 and '#define GWTF_ABI_VERSION 11' in header
+    assert _lib.ABI_VERSION == 12 and '#define GWTF_ABI_VERSION 12' in header
     body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct GwtfImageArgs \{(.*?)\} GwtfImageArgs;', header, re.S).group(1), flags=re.S)
     names = []
     for decl in filter(None, (d.strip() for d in body.split(';'))):
         names += [re.search(r'(\w+)\s*(?:\[\d+\])?$', piece.strip()).group(1) for piece in decl.split(',')]
     assert names == [n for n, _ in _lib.ImageArgs._fields_] and len(names) == 28
     L = _lib.lib()
-    assert L.gwtf_abi_version() == 11
+    assert L.gwtf_abi_version() == 12
     assert L.gwtf_transform_images(None) == 10001
     fake = 0x1000                                     # never dereferenced: every check below fails before anything is launched
     ok = dict(images=fake, out=fake, B=2, n_images=4, C=3, H=9, W=7, H_r=9, W_r=7)

@@ -31,9 +31,9 @@ def test_header_declares_the_entry_points_and_the_library_exports_them():
     assert 'gwtf_norm2d.hip' in re.search(r'^SRCS := (.*)$', makefile, re.M).group(1).split()
 
 
-def test_abi_version_stays_11():
-    assert _lib.ABI_VERSION == 11 and _lib.lib().gwtf_abi_version() == 11
-    assert re.search(r'#define GWTF_ABI_VERSION 11\b', _header())
+def test_abi_version_is_12():
+    assert _lib.ABI_VERSION == 12 and _lib.lib().gwtf_abi_version() == 12
+    assert re.search(r'#define GWTF_ABI_VERSION 12\b', _header())
 
 
 def _c_struct_fields(header, name):

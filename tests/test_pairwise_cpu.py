@@ -70,7 +70,7 @@ def test_new_entries_are_declared_and_bound():
     declared = set(re.findall(r'\b(gwtf_[a-z0-9_]+)\s*\(', header))
     for name in ('gwtf_chamfer_directed', 'gwtf_emd_cost_pairs'):
         assert name in declared and name in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 11 and '#define GWTF_ABI_VERSION 11' in header
+    assert _lib.ABI_VERSION == 12 and '#define GWTF_ABI_VERSION 12' in header
     # malformed arguments never reach a launch (host-side checks of the library, no GPU needed)
     L = _lib.lib()
     assert L.gwtf_chamfer_directed(None, None, None, None, None, 0, 1, 1, 1, 1, None) == 10001

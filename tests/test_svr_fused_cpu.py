@@ -1,6 +1,7 @@
-"""Host side of the fused single-view-reconstruction training path: the per-row latent-loss exports (csrc/gwtf_latent.hip) are
-declared, bound and exported, and every argument check of Flow_Mixture_SVR_Model.forward_fused / GraphedTrainStep(images_example=)
+"""Host side of the fused single-view-reconstruction training path: the latent-loss exports (csrc/gwtf_latent.hip: one record, the
+per-row base Gaussian its `rows` field) are declared, bound and exported, and every argument check of Flow_Mixture_SVR_Model.forward_fused / GraphedTrainStep(images_example=)
 fires before any device work.  No GPU: a check that came after a device call would fail here with another exception."""
+import ctypes
 import json
 import os
 import re
@@ -12,7 +13,7 @@ from conftest import GOLDEN, ROOT
 from go_with_the_flows_amd import _lib, models
 from go_with_the_flows_amd.training import GraphedTrainStep
 
-NEW = ('gwtf_latent_loss_rows_forward', 'gwtf_latent_loss_rows_backward')
+NEW = ('gwtf_latent_loss_forward', 'gwtf_latent_loss_backward')
 
 
 def small_cfg(**over):
@@ -36,21 +37,26 @@ def inputs(B=2, N=8, side=32):
 def test_exports_are_declared_bound_and_exported_without_an_abi_bump():
     header = open(os.path.join(ROOT, 'include', 'gwtf.h')).read()
     declared = set(re.findall(r'\b(gwtf_[a-z0-9_]+)\s*\(', header))
-    for name, old in zip(NEW, ('gwtf_latent_loss_forward', 'gwtf_latent_loss_backward')):
+    for name in NEW:
         assert name in declared and name in _lib._SIGNATURES and name in _lib.EXPORTS
-        assert _lib._SIGNATURES[name] == _lib._SIGNATURES[old]          # the arguments mirror the shared-base pair
-    assert _lib.ABI_VERSION == 11 and '#define GWTF_ABI_VERSION 11' in header
+        assert _lib._SIGNATURES[name] == (ctypes.c_int, [ctypes.c_void_p])     # both families: one record, its `rows` field
+    assert 'rows' in dict(_lib.LatentLossArgs._fields_)
+    assert _lib.ABI_VERSION == 12 and '#define GWTF_ABI_VERSION 12' in header
     L = _lib.lib()
-    assert L.gwtf_abi_version() == 11
+    assert L.gwtf_abi_version() == 12
     for name in NEW:
         assert hasattr(L, name)
     # argument checks of the launchers: nothing is launched on a refused call
     fake = 0x1000
-    assert L.gwtf_latent_loss_rows_forward(*([None] * 8), 2, 2, 2, 1.0, 1.0, 1.0, None) == 10001
-    assert L.gwtf_latent_loss_rows_backward(*([None] * 10), 2, 2, 2, 1.0, 1.0, 1.0, None) == 10001
-    for B, G, n2 in ((0, 2, 2), (2, 0, 2), (2, 2, 0), (1 << 20, 1 << 12, 1)):     # the last: B * G does not fit the element index
-        assert L.gwtf_latent_loss_rows_forward(*([fake] * 8), B, G, n2, 1.0, 1.0, 1.0, None) == 10001
-        assert L.gwtf_latent_loss_rows_backward(*([fake] * 10), B, G, n2, 1.0, 1.0, 1.0, None) == 10001
+    pointers = [n for n, t in _lib.LatentLossArgs._fields_ if t is ctypes.c_void_p and n != 'stream']
+    for rows in (0, 1):
+        null = _lib.LatentLossArgs(B=2, G=2, n2=2, rows=rows, pw=1.0, gw=1.0, ew=1.0)
+        assert L.gwtf_latent_loss_forward(ctypes.byref(null)) == 10001
+        assert L.gwtf_latent_loss_backward(ctypes.byref(null)) == 10001
+        for B, G, n2 in ((0, 2, 2), (2, 0, 2), (2, 2, 0), (1 << 20, 1 << 12, 1)):     # the last: B * G does not fit the element index
+            a = _lib.LatentLossArgs(B=B, G=G, n2=n2, rows=rows, pw=1.0, gw=1.0, ew=1.0, **{n: fake for n in pointers})
+            assert L.gwtf_latent_loss_forward(ctypes.byref(a)) == 10001
+            assert L.gwtf_latent_loss_backward(ctypes.byref(a)) == 10001
 
 
 def test_rows_function_names_all_shapes_in_its_error():
