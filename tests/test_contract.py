@@ -89,7 +89,8 @@ def test_ctypes_records_follow_the_header_field_for_field():
     for c_name, mirror, at_least in (('GwtfStackArgs', _lib.StackArgs, 22), ('GwtfTrainCtx', _lib.TrainCtx, 43),
                                      ('GwtfEncTrainCtx', _lib.EncTrainCtx, 47), ('GwtfCloudArgs', _lib.CloudArgs, 31),
                                      ('GwtfRouteArgs', _lib.RouteArgs, 20), ('GwtfRoutedStackArgs', _lib.RoutedStackArgs, 17),
-                                     ('GwtfHeadArgs', _lib.HeadArgs, 28), ('GwtfLatentLossArgs', _lib.LatentLossArgs, 23)):
+                                     ('GwtfHeadArgs', _lib.HeadArgs, 28), ('GwtfLatentLossArgs', _lib.LatentLossArgs, 23),
+                                     ('GwtfImageArgs', _lib.ImageArgs, 28), ('GwtfNorm2dArgs', _lib.Norm2dArgs, 24)):
         declared = _c_struct_fields(header, c_name)
         assert len(declared) >= at_least, c_name
         assert _mirror_fields(mirror) == declared, c_name
