@@ -108,6 +108,10 @@ _SIGNATURES = {
     'gwtf_norm2d_partials': (ctypes.c_int, [ctypes.c_int] * 4),
     'gwtf_norm2d_forward': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_norm2d_backward': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_norm2d_forward_sums': (ctypes.c_int, [ctypes.c_void_p, _c_fp]),
+    'gwtf_norm2d_forward_apply': (ctypes.c_int, [ctypes.c_void_p, _c_fp, ctypes.c_double]),
+    'gwtf_norm2d_backward_sums': (ctypes.c_int, [ctypes.c_void_p, _c_fp]),
+    'gwtf_norm2d_backward_apply': (ctypes.c_int, [ctypes.c_void_p, _c_fp, ctypes.c_double]),
 }
 
 PHASE_FWD_INIT, PHASE_FWD_A, PHASE_FWD_B, PHASE_BWD_A, PHASE_BWD_B, PHASE_BWD_C = range(6)

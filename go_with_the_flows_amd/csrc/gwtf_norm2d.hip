@@ -21,6 +21,11 @@
 // A thread takes four consecutive floats as one 16-byte access when planes are a multiple of four floats and every base address is
 // 16-byte aligned; otherwise (7 x 7 planes) one float at a time.  One 32-bit division per access finds the plane.
 // No atomics, no scratch, no device-side allocation: two runs give the same bits.
+//
+// Statistics over several ranks (SyncBatchNorm): each direction as two calls around the caller's sum over the ranks.  *_sums runs the
+// partial-sum launch and folds the S partials into this rank's float64 (C, 2) sums; *_apply finalises from the totals and the global
+// count and runs the same applying launch.  The kernels of the one-rank calls are launched unchanged; three one-thread-per-channel
+// launches are new (fold, finalise from sums, the totals as floats for the backward's applying launch).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -148,11 +153,8 @@ __global__ __launch_bounds__(kThreads) void partials_kernel(GwtfNorm2dArgs p, un
   }
 }
 
-__global__ __launch_bounds__(kThreads) void finalize_forward_kernel(GwtfNorm2dArgs p, int S, double count) {
-  const int c = blockIdx.x * kThreads + threadIdx.x;
-  if (c >= p.C) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int s = 0; s < S; ++s) { s1 += p.partials[((size_t)c * S + s) * 2]; s2 += p.partials[((size_t)c * S + s) * 2 + 1]; }
+// Channel c's statistics from its sums over `count` values: stats and the running statistics.
+__device__ __forceinline__ void finalize_channel(const GwtfNorm2dArgs& p, int c, double s1, double s2, double count) {
   const double mean = s1 / count;
   double var = s2 / count - mean * mean;
   if (var < 0.0) var = 0.0;
@@ -163,6 +165,42 @@ __global__ __launch_bounds__(kThreads) void finalize_forward_kernel(GwtfNorm2dAr
   const double mom = (double)p.momentum;
   if (p.running_mean) p.running_mean[c] = (float)((1.0 - mom) * (double)p.running_mean[c] + mom * mean);
   if (p.running_var) p.running_var[c] = (float)((1.0 - mom) * (double)p.running_var[c] + mom * (var * count / (count - 1.0)));
+}
+
+__global__ __launch_bounds__(kThreads) void finalize_forward_kernel(GwtfNorm2dArgs p, int S, double count) {
+  const int c = blockIdx.x * kThreads + threadIdx.x;
+  if (c >= p.C) return;
+  double s1 = 0.0, s2 = 0.0;
+  for (int s = 0; s < S; ++s) { s1 += p.partials[((size_t)c * S + s) * 2]; s2 += p.partials[((size_t)c * S + s) * 2 + 1]; }
+  finalize_channel(p, c, s1, s2, count);
+}
+
+// ---- statistics over several ranks: the finalising launches split where the caller sums over the ranks ----------------------------
+// This rank's sums of channel c, the S partials added in the order of the finalising kernels above.  BWD: also the rank-local
+// parameter gradients, as finalize_backward_kernel writes them.
+template <bool BWD>
+__global__ __launch_bounds__(kThreads) void fold_sums_kernel(GwtfNorm2dArgs p, int S, double* sums) {
+  const int c = blockIdx.x * kThreads + threadIdx.x;
+  if (c >= p.C) return;
+  double s1 = 0.0, s2 = 0.0;
+  for (int s = 0; s < S; ++s) { s1 += p.partials[((size_t)c * S + s) * 2]; s2 += p.partials[((size_t)c * S + s) * 2 + 1]; }
+  sums[2 * c] = s1;
+  sums[2 * c + 1] = s2;
+  if (BWD) { p.dbeta[c] = (float)s1; p.dgamma[c] = (float)s2; }
+}
+
+__global__ __launch_bounds__(kThreads) void finalize_from_sums_kernel(GwtfNorm2dArgs p, const double* sums, double count) {
+  const int c = blockIdx.x * kThreads + threadIdx.x;
+  if (c >= p.C) return;
+  finalize_channel(p, c, sums[2 * c], sums[2 * c + 1], count);
+}
+
+// The totals as floats, [2][C]: what apply_backward_kernel reads through dbeta / dgamma.
+__global__ __launch_bounds__(kThreads) void float_sums_kernel(const double* sums, float* out, int C) {
+  const int c = blockIdx.x * kThreads + threadIdx.x;
+  if (c >= C) return;
+  out[c] = (float)sums[2 * c];
+  out[C + c] = (float)sums[2 * c + 1];
 }
 
 __global__ __launch_bounds__(kThreads) void finalize_backward_kernel(GwtfNorm2dArgs p, int S) {
@@ -305,18 +343,19 @@ int split_of(long long nhw, int C) {
   return s < 1 ? 1 : (int)s;
 }
 
-int check_sizes(int N, int C, int H, int W) {
+// least: the values per channel this rank must hold (2; 1 when the statistics cover other ranks' images as well)
+int check_sizes(int N, int C, int H, int W, long long least = 2) {
   if (N < 1 || C < 1 || H < 1 || W < 1 || N > 65535) return GWTF_E_BADARG;
   const long long hw = (long long)H * W, nhw = (long long)N * hw, chw = (long long)C * hw;
   if (nhw >= (1LL << 31) - 4LL * kMaxSplit - kThreads * 4 || chw >= (1LL << 31) - kThreads * kQuads * 4) return GWTF_E_BADARG;
-  if (nhw < 2) return GWTF_E_FEW_VALUES;
+  if (nhw < least) return GWTF_E_FEW_VALUES;
   return 0;
 }
 
-int check_common(const GwtfNorm2dArgs* pa) {
+int check_common(const GwtfNorm2dArgs* pa, long long least = 2) {
   if (!pa) return GWTF_E_BADARG;
   const GwtfNorm2dArgs& a = *pa;
-  const int e = check_sizes(a.N, a.C, a.H, a.W);
+  const int e = check_sizes(a.N, a.C, a.H, a.W, least);
   if (e) return e;
   if (!a.x || !a.gamma || !a.stats || !a.partials) return GWTF_E_BADARG;
   if (a.pool && (!a.relu || a.residual || a.d_residual || !a.offsets)) return GWTF_E_BADARG;
@@ -325,6 +364,112 @@ int check_common(const GwtfNorm2dArgs* pa) {
 }
 
 bool aligned16(const void* q) { return ((uintptr_t)q & 15u) == 0; }
+
+// What the launches of one call share: the stream, the sizes, the split of the partial sums.
+struct Work {
+  hipStream_t st;
+  unsigned hw, nhw, chw, per;
+  int S;
+};
+
+Work work_of(const GwtfNorm2dArgs& a) {
+  Work w;
+  w.st = (hipStream_t)a.stream;
+  w.hw = (unsigned)(a.H * a.W); w.nhw = (unsigned)a.N * w.hw; w.chw = (unsigned)a.C * w.hw;
+  w.S = split_of(w.nhw, a.C);
+  w.per = ((w.nhw + w.S - 1) / w.S + 3u) & ~3u;
+  return w;
+}
+
+dim3 channel_grid(int C) { return dim3((C + kThreads - 1) / kThreads); }
+
+// The totals over the ranks and the number of values they cover.
+int check_totals(const double* sums, double count, const Work& w) {
+  if (!sums) return GWTF_E_BADARG;
+  if (!(count >= 2.0)) return GWTF_E_FEW_VALUES;
+  if (count < (double)w.nhw) return GWTF_E_BADARG;
+  return 0;
+}
+
+void launch_forward_partials(const GwtfNorm2dArgs& a, const Work& w) {
+  const bool vec_x = w.hw % 4 == 0 && aligned16(a.x);
+  if (vec_x) hipLaunchKernelGGL((partials_kernel<true, false, kPlain>), dim3(a.C, w.S), dim3(kThreads), 0, w.st, a, w.nhw, w.per);
+  else hipLaunchKernelGGL((partials_kernel<false, false, kPlain>), dim3(a.C, w.S), dim3(kThreads), 0, w.st, a, w.nhw, w.per);
+}
+
+void launch_forward_apply(const GwtfNorm2dArgs& a, const Work& w) {
+  hipStream_t st = w.st;
+  const unsigned chw = w.chw;
+  if (a.pool) {
+    const unsigned cpool = (unsigned)a.C * pooled(a.H) * pooled(a.W);
+    hipLaunchKernelGGL(apply_forward_pool_kernel, dim3((cpool + kThreads - 1) / kThreads, a.N), dim3(kThreads), 0, st, a, cpool);
+    return;
+  }
+  const bool vec = w.hw % 4 == 0 && aligned16(a.x) && aligned16(a.y) && (!a.residual || aligned16(a.residual));
+  const unsigned tile = kThreads * kQuads * (vec ? 4 : 1);
+  const dim3 grid((chw + tile - 1) / tile, a.N), block(kThreads);
+#define GWTF_NORM2D_FWD(V, R, S_) hipLaunchKernelGGL((apply_forward_kernel<V, R, S_>), grid, block, 0, st, a, chw)
+  const bool relu = a.relu != 0, res = a.residual != nullptr;
+  if (vec) {
+    if (relu) { if (res) GWTF_NORM2D_FWD(true, true, true); else GWTF_NORM2D_FWD(true, true, false); }
+    else { if (res) GWTF_NORM2D_FWD(true, false, true); else GWTF_NORM2D_FWD(true, false, false); }
+  } else {
+    if (relu) { if (res) GWTF_NORM2D_FWD(false, true, true); else GWTF_NORM2D_FWD(false, true, false); }
+    else { if (res) GWTF_NORM2D_FWD(false, false, true); else GWTF_NORM2D_FWD(false, false, false); }
+  }
+#undef GWTF_NORM2D_FWD
+}
+
+int backward_mode(const GwtfNorm2dArgs& a) { return a.pool ? kPool : (a.relu ? kMask : kPlain); }
+
+// What either backward launch reads besides x, gamma and stats.
+bool backward_reads_ok(const GwtfNorm2dArgs& a) {
+  if (!a.dy) return false;
+  if (a.relu && !a.pool && !a.y) return false;                      // the mask is read from the saved output
+  if (a.pool && !a.beta) return false;                              // the recomputation needs the forward's shift
+  return true;
+}
+
+// One access width for both backward launches (a NULL dx counts as aligned: the split entry points pass one record to both calls).
+bool backward_vec(const GwtfNorm2dArgs& a, const Work& w) {
+  const int mode = backward_mode(a);
+  // with pool a quad may run over a row's end into the next row (handled) but never over two: W >= 4
+  bool vec = w.hw % 4 == 0 && aligned16(a.x) && aligned16(a.dx) && (!a.d_residual || aligned16(a.d_residual));
+  if (mode == kPool) vec = vec && a.W >= 4;
+  else vec = vec && aligned16(a.dy) && (mode != kMask || aligned16(a.y));
+  return vec;
+}
+
+void launch_backward_partials(const GwtfNorm2dArgs& a, const Work& w) {
+  const int mode = backward_mode(a);
+  const dim3 pgrid(a.C, w.S), block(kThreads);
+#define GWTF_NORM2D_PART(V, M) hipLaunchKernelGGL((partials_kernel<V, true, M>), pgrid, block, 0, w.st, a, w.nhw, w.per)
+  if (backward_vec(a, w)) { if (mode == kPool) GWTF_NORM2D_PART(true, kPool); else if (mode == kMask) GWTF_NORM2D_PART(true, kMask); else GWTF_NORM2D_PART(true, kPlain); }
+  else { if (mode == kPool) GWTF_NORM2D_PART(false, kPool); else if (mode == kMask) GWTF_NORM2D_PART(false, kMask); else GWTF_NORM2D_PART(false, kPlain); }
+#undef GWTF_NORM2D_PART
+}
+
+// dbeta / dgamma of the record: the two sums over all `1 / inv_count` values, as floats.
+void launch_backward_apply(const GwtfNorm2dArgs& a, const Work& w, float inv_count) {
+  const int mode = backward_mode(a);
+  const bool vec = backward_vec(a, w);
+  hipStream_t st = w.st;
+  const unsigned chw = w.chw;
+  const unsigned tile = kThreads * kQuads * (vec ? 4 : 1);
+  const dim3 grid((chw + tile - 1) / tile, a.N), block(kThreads);
+  const bool res = a.d_residual != nullptr;
+#define GWTF_NORM2D_BWD(V, M, R) hipLaunchKernelGGL((apply_backward_kernel<V, M, R>), grid, block, 0, st, a, chw, inv_count)
+  if (vec) {
+    if (mode == kPool) GWTF_NORM2D_BWD(true, kPool, false);
+    else if (mode == kMask) { if (res) GWTF_NORM2D_BWD(true, kMask, true); else GWTF_NORM2D_BWD(true, kMask, false); }
+    else { if (res) GWTF_NORM2D_BWD(true, kPlain, true); else GWTF_NORM2D_BWD(true, kPlain, false); }
+  } else {
+    if (mode == kPool) GWTF_NORM2D_BWD(false, kPool, false);
+    else if (mode == kMask) { if (res) GWTF_NORM2D_BWD(false, kMask, true); else GWTF_NORM2D_BWD(false, kMask, false); }
+    else { if (res) GWTF_NORM2D_BWD(false, kPlain, true); else GWTF_NORM2D_BWD(false, kPlain, false); }
+  }
+#undef GWTF_NORM2D_BWD
+}
 
 }  // namespace
 
@@ -338,32 +483,33 @@ extern "C" int gwtf_norm2d_forward(const GwtfNorm2dArgs* pa) {
   if (bad) return bad;
   const GwtfNorm2dArgs& a = *pa;
   if (!a.beta || !a.y) return GWTF_E_BADARG;
-  hipStream_t st = (hipStream_t)a.stream;
-  const unsigned hw = (unsigned)(a.H * a.W), nhw = (unsigned)a.N * hw, chw = (unsigned)a.C * hw;
-  const int S = split_of(nhw, a.C);
-  const unsigned per = ((nhw + S - 1) / S + 3u) & ~3u;
-  const bool vec_x = hw % 4 == 0 && aligned16(a.x);
-  const bool vec = vec_x && aligned16(a.y) && (!a.residual || aligned16(a.residual));
-  if (vec_x) hipLaunchKernelGGL((partials_kernel<true, false, kPlain>), dim3(a.C, S), dim3(kThreads), 0, st, a, nhw, per);
-  else hipLaunchKernelGGL((partials_kernel<false, false, kPlain>), dim3(a.C, S), dim3(kThreads), 0, st, a, nhw, per);
-  hipLaunchKernelGGL(finalize_forward_kernel, dim3((a.C + kThreads - 1) / kThreads), dim3(kThreads), 0, st, a, S, (double)nhw);
-  if (a.pool) {
-    const unsigned cpool = (unsigned)a.C * pooled(a.H) * pooled(a.W);
-    hipLaunchKernelGGL(apply_forward_pool_kernel, dim3((cpool + kThreads - 1) / kThreads, a.N), dim3(kThreads), 0, st, a, cpool);
-    return (int)hipGetLastError();
-  }
-  const unsigned tile = kThreads * kQuads * (vec ? 4 : 1);
-  const dim3 grid((chw + tile - 1) / tile, a.N), block(kThreads);
-#define GWTF_NORM2D_FWD(V, R, S_) hipLaunchKernelGGL((apply_forward_kernel<V, R, S_>), grid, block, 0, st, a, chw)
-  const bool relu = a.relu != 0, res = a.residual != nullptr;
-  if (vec) {
-    if (relu) { if (res) GWTF_NORM2D_FWD(true, true, true); else GWTF_NORM2D_FWD(true, true, false); }
-    else { if (res) GWTF_NORM2D_FWD(true, false, true); else GWTF_NORM2D_FWD(true, false, false); }
-  } else {
-    if (relu) { if (res) GWTF_NORM2D_FWD(false, true, true); else GWTF_NORM2D_FWD(false, true, false); }
-    else { if (res) GWTF_NORM2D_FWD(false, false, true); else GWTF_NORM2D_FWD(false, false, false); }
-  }
-#undef GWTF_NORM2D_FWD
+  const Work w = work_of(a);
+  launch_forward_partials(a, w);
+  hipLaunchKernelGGL(finalize_forward_kernel, channel_grid(a.C), dim3(kThreads), 0, w.st, a, w.S, (double)w.nhw);
+  launch_forward_apply(a, w);
+  return (int)hipGetLastError();
+}
+
+extern "C" int gwtf_norm2d_forward_sums(const GwtfNorm2dArgs* pa, double* sums) {
+  const int bad = check_common(pa, 1);
+  if (bad) return bad;
+  if (!sums) return GWTF_E_BADARG;
+  const GwtfNorm2dArgs& a = *pa;
+  const Work w = work_of(a);
+  launch_forward_partials(a, w);
+  hipLaunchKernelGGL(fold_sums_kernel<false>, channel_grid(a.C), dim3(kThreads), 0, w.st, a, w.S, sums);
+  return (int)hipGetLastError();
+}
+
+extern "C" int gwtf_norm2d_forward_apply(const GwtfNorm2dArgs* pa, const double* sums, double count) {
+  int bad = check_common(pa, 1);
+  if (bad) return bad;
+  const GwtfNorm2dArgs& a = *pa;
+  if (!a.beta || !a.y) return GWTF_E_BADARG;
+  const Work w = work_of(a);
+  if ((bad = check_totals(sums, count, w))) return bad;
+  hipLaunchKernelGGL(finalize_from_sums_kernel, channel_grid(a.C), dim3(kThreads), 0, w.st, a, sums, count);
+  launch_forward_apply(a, w);
   return (int)hipGetLastError();
 }
 
@@ -371,38 +517,38 @@ extern "C" int gwtf_norm2d_backward(const GwtfNorm2dArgs* pa) {
   const int bad = check_common(pa);
   if (bad) return bad;
   const GwtfNorm2dArgs& a = *pa;
-  if (!a.dy || !a.dx || !a.dgamma || !a.dbeta) return GWTF_E_BADARG;
-  if (a.relu && !a.pool && !a.y) return GWTF_E_BADARG;              // the mask is read from the saved output
-  if (a.pool && !a.beta) return GWTF_E_BADARG;                      // the recomputation needs the forward's shift
-  hipStream_t st = (hipStream_t)a.stream;
-  const unsigned hw = (unsigned)(a.H * a.W), nhw = (unsigned)a.N * hw, chw = (unsigned)a.C * hw;
-  const int S = split_of(nhw, a.C);
-  const unsigned per = ((nhw + S - 1) / S + 3u) & ~3u;
-  const int mode = a.pool ? kPool : (a.relu ? kMask : kPlain);
-  // with pool a quad may run over a row's end into the next row (handled) but never over two: W >= 4
-  bool vec = hw % 4 == 0 && aligned16(a.x) && aligned16(a.dx) && (!a.d_residual || aligned16(a.d_residual));
-  if (mode == kPool) vec = vec && a.W >= 4;
-  else vec = vec && aligned16(a.dy) && (mode != kMask || aligned16(a.y));
-  const dim3 pgrid(a.C, S), block(kThreads);
-#define GWTF_NORM2D_PART(V, M) hipLaunchKernelGGL((partials_kernel<V, true, M>), pgrid, block, 0, st, a, nhw, per)
-  if (vec) { if (mode == kPool) GWTF_NORM2D_PART(true, kPool); else if (mode == kMask) GWTF_NORM2D_PART(true, kMask); else GWTF_NORM2D_PART(true, kPlain); }
-  else { if (mode == kPool) GWTF_NORM2D_PART(false, kPool); else if (mode == kMask) GWTF_NORM2D_PART(false, kMask); else GWTF_NORM2D_PART(false, kPlain); }
-#undef GWTF_NORM2D_PART
-  hipLaunchKernelGGL(finalize_backward_kernel, dim3((a.C + kThreads - 1) / kThreads), block, 0, st, a, S);
-  const unsigned tile = kThreads * kQuads * (vec ? 4 : 1);
-  const dim3 grid((chw + tile - 1) / tile, a.N);
-  const float inv_count = (float)(1.0 / (double)nhw);
-  const bool res = a.d_residual != nullptr;
-#define GWTF_NORM2D_BWD(V, M, R) hipLaunchKernelGGL((apply_backward_kernel<V, M, R>), grid, block, 0, st, a, chw, inv_count)
-  if (vec) {
-    if (mode == kPool) GWTF_NORM2D_BWD(true, kPool, false);
-    else if (mode == kMask) { if (res) GWTF_NORM2D_BWD(true, kMask, true); else GWTF_NORM2D_BWD(true, kMask, false); }
-    else { if (res) GWTF_NORM2D_BWD(true, kPlain, true); else GWTF_NORM2D_BWD(true, kPlain, false); }
-  } else {
-    if (mode == kPool) GWTF_NORM2D_BWD(false, kPool, false);
-    else if (mode == kMask) { if (res) GWTF_NORM2D_BWD(false, kMask, true); else GWTF_NORM2D_BWD(false, kMask, false); }
-    else { if (res) GWTF_NORM2D_BWD(false, kPlain, true); else GWTF_NORM2D_BWD(false, kPlain, false); }
-  }
-#undef GWTF_NORM2D_BWD
+  if (!a.dx || !a.dgamma || !a.dbeta) return GWTF_E_BADARG;
+  if (!backward_reads_ok(a)) return GWTF_E_BADARG;
+  const Work w = work_of(a);
+  launch_backward_partials(a, w);
+  hipLaunchKernelGGL(finalize_backward_kernel, channel_grid(a.C), dim3(kThreads), 0, w.st, a, w.S);
+  launch_backward_apply(a, w, (float)(1.0 / (double)w.nhw));
+  return (int)hipGetLastError();
+}
+
+extern "C" int gwtf_norm2d_backward_sums(const GwtfNorm2dArgs* pa, double* sums) {
+  const int bad = check_common(pa, 1);
+  if (bad) return bad;
+  const GwtfNorm2dArgs& a = *pa;
+  if (!sums || !a.dgamma || !a.dbeta || !backward_reads_ok(a)) return GWTF_E_BADARG;
+  const Work w = work_of(a);
+  launch_backward_partials(a, w);
+  hipLaunchKernelGGL(fold_sums_kernel<true>, channel_grid(a.C), dim3(kThreads), 0, w.st, a, w.S, sums);
+  return (int)hipGetLastError();
+}
+
+extern "C" int gwtf_norm2d_backward_apply(const GwtfNorm2dArgs* pa, const double* sums, double count) {
+  int bad = check_common(pa, 1);
+  if (bad) return bad;
+  if (!pa->dx || !backward_reads_ok(*pa)) return GWTF_E_BADARG;
+  const Work w = work_of(*pa);
+  if ((bad = check_totals(sums, count, w))) return bad;
+  // the applying launch reads the two sums through dbeta / dgamma: the totals, as floats, in the partials' space ([C][S][2] doubles
+  // hold 2 C floats for every S >= 1); this rank's dbeta / dgamma stay as backward_sums left them
+  GwtfNorm2dArgs a = *pa;
+  a.dbeta = reinterpret_cast<float*>(a.partials);
+  a.dgamma = a.dbeta + a.C;
+  hipLaunchKernelGGL(float_sums_kernel, channel_grid(a.C), dim3(kThreads), 0, w.st, sums, a.dbeta, a.C);
+  launch_backward_apply(a, w, (float)(1.0 / count));
   return (int)hipGetLastError();
 }

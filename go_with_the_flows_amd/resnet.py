@@ -11,8 +11,10 @@ Two paths, the split the PointNet encoder had before its training kernels:
 * train mode, or whenever a gradient must flow through the encoder: the plain torch modules (library convolutions, batch
   statistics, autograd).  With the class attribute ``ResNet.train_norm = 'hip'`` (default ``'library'``) a train-mode call keeps the
   library convolutions but runs every BatchNorm2d with the ReLU, residual add and stem max-pool behind it through the fused
-  kernels of csrc/gwtf_norm2d.hip (norm2d.norm_act_2d), forward and backward; the head stays on the modules.  Convolution
-  backward in HIP and SyncBatchNorm are not built.
+  kernels of csrc/gwtf_norm2d.hip (norm2d.norm_act_2d), forward and backward; the head stays on the modules.  After
+  ``nn.SyncBatchNorm.convert_sync_batchnorm`` in a data-parallel run the same path takes its batch statistics over the images of all
+  ranks (one all-reduce of the float64 sums per layer and direction; the head on the gathered rows).  Convolution backward in HIP
+  is not built.
 ``forward_torch`` runs the module graph on any device and dtype (the CPU float64 evaluation the tests compare against).
 An eval-mode call that the kernels cannot take (CPU tensor, dtype other than float32, channels other than 4, images under
 32 x 32) raises GwtfError: there is no fallback.
@@ -137,8 +139,24 @@ class ResNet(nn.Module):
                 y = norm_act_2d(_conv(blk.conv1, x), blk.bn1)
                 r = x if blk.downsample is None else norm_act_2d(_conv(blk.downsample[0], x), blk.downsample[1], relu=False)
                 x = norm_act_2d(_conv(blk.conv2, y), blk.bn2, residual=r)
-        x = torch.flatten(self.avgpool(x), 1)
-        return self.relu(self.fc_bn(self.fc(x)))
+        return self._head_train(torch.flatten(self.avgpool(x), 1))
+
+    def _head_train(self, x):
+        """fc -> fc_bn -> ReLU on the pooled rows.  In a synchronised data-parallel run (fc_bn a SyncBatchNorm) every rank evaluates
+        the head on the pooled rows of ALL ranks and keeps its own (dist.gather_rows, as the per-shape heads do): fc_bn needs no
+        collective of its own and every rank leaves the same running statistics."""
+        from .dist import gather_rows, syncs_statistics
+        bn = self.fc_bn
+        if not syncs_statistics([bn]):
+            return self.relu(bn(self.fc(x)))
+        if bn.momentum is None or not bn.track_running_stats:
+            raise GwtfError('the synchronised head takes an fc_bn with a momentum that tracks running statistics')
+        rows = x.shape[0]
+        x, lay = gather_rows(x)
+        h = F.batch_norm(self.fc(x), bn.running_mean, bn.running_var, bn.weight, bn.bias, True, bn.momentum, bn.eps)
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+        return F.relu(h[lay.row0:lay.row0 + rows])
 
     # ---- packed weights (BatchNorm folded in float64 on the host), cached per parameter version ----
     def invalidate_packed_weights(self):

@@ -21,6 +21,7 @@ class GraphedTrainStep:
     """step = GraphedTrainStep(model, criterion, optimizer, g_example, p_example); loss, pnll, gnll, gent = step(g, p).
     Single-view reconstruction (a model with an ``img_encoder``): ``GraphedTrainStep(..., images_example=images)`` and
     ``step(g, p, images)``; the image encoder's library convolutions and their autograd backward are captured with the rest.
+    Data-parallel SVR steps need ``model.img_encoder.train_norm = 'hip'``: the fused BatchNorm2d kernels all-reduce their sums.
 
     * inputs are copied into static buffers, so every batch must have the example's shape (drop the ragged last batch,
       as the reference's DataLoader does with drop_last=True, train_ae.py:97);
@@ -40,8 +41,10 @@ class GraphedTrainStep:
             raise ValueError(f'images_example was given, but {type(model).__name__} has no img_encoder')
         # data_parallel=None: decided by the process group (more than one rank, or GWTF_FORCE_SHARDED=1)
         data_parallel = sharded() if data_parallel is None else data_parallel
-        if images_example is not None and data_parallel:
-            raise NotImplementedError('multi-rank SVR training is not built')
+        if images_example is not None and data_parallel and getattr(model.img_encoder, 'train_norm', None) != 'hip':
+            raise NotImplementedError("multi-rank SVR training is not built on the library BatchNorm2d path: set "
+                                      "model.img_encoder.train_norm = 'hip' (the fused kernels sum their batch statistics over the "
+                                      "ranks), the supported setting")
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
         self.reducer = OverlappedGradients(model, average=average_gradients) if data_parallel else None
         self.g_static, self.p_static = g_example.clone(), p_example.clone()

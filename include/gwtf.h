@@ -805,6 +805,27 @@ int gwtf_norm2d_partials(int N, int C, int H, int W);
 int gwtf_norm2d_forward(const GwtfNorm2dArgs* args);
 int gwtf_norm2d_backward(const GwtfNorm2dArgs* args);
 
+/* The same layer with batch statistics over the images of SEVERAL ranks (SyncBatchNorm; added without a version change, no existing
+ * record or signature moved).  Each direction is split where the statistics become global: *_sums leaves this rank's float64 sums in
+ * sums = [C][2] -- the caller adds them up over the ranks -- and *_apply takes the totals and `count`, the number of values per
+ * channel over all ranks.  Pass the same record to both calls of a direction.
+ *   forward_sums    the partial-sum launch of gwtf_norm2d_forward over this rank's N images, then one thread per channel adds the S
+ *                   partials in that call's order: sums[c] = {sum x, sum x * x}.  Nothing else is written.
+ *   forward_apply   stats, running_mean and running_var from the totals by gwtf_norm2d_forward's arithmetic (the unbiased variance
+ *                   takes the global count), then its applying launch on the local images.
+ *   backward_sums   the backward's partial-sum launch, folded: sums[c] = {sum dy', sum dy' * xhat}, and the rank-local dbeta /
+ *                   dgamma (the floats of those sums): parameter gradients stay local, as torch's SyncBatchNorm leaves them.
+ *   backward_apply  dx = gamma * rstd * (dy' - sums[c][0] / count - xhat * sums[c][1] / count) and d_residual = dy' by
+ *                   gwtf_norm2d_backward's applying launch; the first 2 * C floats of `partials` are overwritten (the totals as floats,
+ *                   which that launch reads in place of dbeta / dgamma; those two are not touched).
+ * One rank, count = N * H * W: the bits of gwtf_norm2d_forward / _backward.  Validation as there, on the host before any launch, except
+ * that a local N * H * W of 1 is taken; further GWTF_E_BADARG: sums NULL, count < N * H * W; GWTF_E_FEW_VALUES: count < 2.  *_sums read
+ * no y (forward), beta (unless pool) or running statistics; backward_apply needs no dgamma / dbeta. */
+int gwtf_norm2d_forward_sums(const GwtfNorm2dArgs* args, double* sums);
+int gwtf_norm2d_forward_apply(const GwtfNorm2dArgs* args, const double* sums, double count);
+int gwtf_norm2d_backward_sums(const GwtfNorm2dArgs* args, double* sums);
+int gwtf_norm2d_backward_apply(const GwtfNorm2dArgs* args, const double* sums, double count);
+
 #ifdef __cplusplus
 }
 #endif
