@@ -112,6 +112,8 @@ _SIGNATURES = {
     'gwtf_norm2d_forward_apply': (ctypes.c_int, [ctypes.c_void_p, _c_fp, ctypes.c_double]),
     'gwtf_norm2d_backward_sums': (ctypes.c_int, [ctypes.c_void_p, _c_fp]),
     'gwtf_norm2d_backward_apply': (ctypes.c_int, [ctypes.c_void_p, _c_fp, ctypes.c_double]),
+    'gwtf_voxel_occupancy': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_jsd_counts': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_int, _c_fp, _c_fp]),
 }
 
 PHASE_FWD_INIT, PHASE_FWD_A, PHASE_FWD_B, PHASE_BWD_A, PHASE_BWD_B, PHASE_BWD_C = range(6)
@@ -223,6 +225,12 @@ class Norm2dArgs(ctypes.Structure):
                                                 'partials', 'dy', 'dx', 'd_residual', 'dgamma', 'dbeta')] +
                 [(n, ctypes.c_int) for n in ('N', 'C', 'H', 'W', 'relu', 'pool')] +
                 [('eps', ctypes.c_float), ('momentum', ctypes.c_float), ('stream', ctypes.c_void_p)])
+
+
+class OccupancyArgs(ctypes.Structure):
+    """GwtfOccupancyArgs of include/gwtf.h (one set of points folded into an occupancy histogram): same field order."""
+    _fields_ = [('points', ctypes.c_void_p), ('n_points', ctypes.c_size_t), ('res', ctypes.c_int), ('edges', ctypes.c_double * 33),
+                ('bound', ctypes.c_float), ('counts', ctypes.c_void_p), ('stats', ctypes.c_void_p), ('stream', ctypes.c_void_p)]
 
 
 EXPORTS = tuple(_SIGNATURES)

@@ -239,7 +239,7 @@ def generate_clouds(model, n_shapes, n_points, batch_size=64, state=None):
     None: the state the model keeps).  Nothing is read back between the batches.
     -> (n_shapes, n_points, 3) float32, contiguous, on the model's device: the layout generation_metrics takes.
     Unlike the reference's loop (evaluating.py:198-203) a cloud that holds NaN is NOT drawn again: looking for one is a host
-    synchronisation per batch.  Check `torch.isfinite(clouds).all()` once at the end if the model may diverge."""
+    synchronisation per batch.  replace_nan_clouds does the reference's replacement on the whole set without one."""
     if getattr(model, 'mode', None) != 'generating':
         raise GwtfError("generate_clouds needs a model in 'generating' mode (model.mode / util_mode)")
     if n_shapes < 1 or n_points < 1 or batch_size < 1:
@@ -251,6 +251,67 @@ def generate_clouds(model, n_shapes, n_points, batch_size=64, state=None):
         g = model.encode(torch.empty(bs, 0, device=dev))['g_prior_samples'][-1]
         out[lo:lo + bs] = model.generate_many(g, n_points, state=state).transpose(1, 2)
     return out
+
+
+def replace_nan_clouds(clouds, generator=None):
+    """evaluating.py:196-202 on the device: every cloud of ``clouds`` ((S, n, 3) float32 on a HIP device) that holds a NaN is replaced
+    by a cloud without NaN of the same set, drawn uniformly with replacement (``generator``: a torch.Generator of that device; None:
+    the device's default one) -> a new (S, n, 3) tensor; clouds without NaN come back bit-equal.  No synchronisation and no shape that
+    depends on the data: the clouds are flagged, a stable sort of the flags lists the good ones first, a uniform draw is scaled by the
+    device-side count of good clouds, and one gather builds the result -- the count of bad clouds never reaches the host.
+    If EVERY cloud holds a NaN the input comes back unchanged (a copy): the reference raises there (np.random.choice on an empty
+    list), which here would take a read-back of that count."""
+    if not torch.is_tensor(clouds) or clouds.dim() != 3 or clouds.shape[2] != 3:
+        raise GwtfError(f'clouds must be an (S, n, 3) tensor, got {tuple(clouds.shape) if torch.is_tensor(clouds) else type(clouds)}')
+    _metrics._ptr(clouds, 'clouds')
+    S, dev = clouds.shape[0], clouds.device
+    if S == 0 or clouds.shape[1] == 0:
+        raise GwtfError('empty point set')
+    bad = torch.isnan(clouds).flatten(1).any(1)                                    # (S,)
+    good_first = torch.sort(bad.to(torch.uint8), stable=True).indices              # the good clouds in their order, then the bad ones
+    n_good = S - bad.sum()                                                         # 0-d, stays on the device
+    u = torch.rand(S, device=dev, dtype=torch.float64, generator=generator)
+    pick = torch.minimum((u * n_good).long(), (n_good - 1).clamp(min=0))           # uniform in [0, n_good)
+    src = torch.where(bad & (n_good > 0), good_first[pick], torch.arange(S, device=dev))
+    return clouds.index_select(0, src)
+
+
+@torch.no_grad()
+def evaluate_generation(model, ref_clouds, n_points=None, batch_size=64, f1_threshold_lst=(0.001,), cd=True, emd=True, f1=True,
+                        jsd=True, state=None, generator=None):
+    """The generating branch of the reference's evaluate (evaluating.py:191-250) in one call, on the device: one generated cloud per
+    cloud of ``ref_clouds`` ((R, n, 3) float32 on the model's device; ``n_points`` per generated cloud, default n) from generate_clouds
+    (``batch_size``, ``state``), replace_nan_clouds (``generator``), the device JSD and generation_metrics.
+    -> the reference's `res` dictionary, same keys and scalings, values as Python floats: 'jsd' (x 1e2); 'cd_mmds' (x 1e4), 'cd_covs',
+    'cd_1nns' (x 1e2); 'emd_mmds', 'emd_covs', 'emd_1nns' (x 1e2); per threshold 'f1_%.4f_mmds' (unscaled), 'f1_%.4f_covs',
+    'f1_%.4f_1nns' (x 1e2).  As in the reference the metric keys are written once per threshold of ``f1_threshold_lst`` (an empty list
+    leaves 'jsd' alone).  Every scaled value is scaled in the tensor's own precision, as the reference scales it, and all of them
+    reach the host in ONE read at the end; before that nothing is read back but what generation_metrics itself reads (coverage
+    counts distinct indices).  The rescaling options of evaluate (unit_scale_evaluation, orig_scale_evaluation) and its h5 saving are
+    not part of this call."""
+    if not torch.is_tensor(ref_clouds) or ref_clouds.dim() != 3 or ref_clouds.shape[2] != 3:
+        raise GwtfError(f'ref_clouds must be an (R, n, 3) tensor, got {tuple(ref_clouds.shape) if torch.is_tensor(ref_clouds) else type(ref_clouds)}')
+    _metrics._ptr(ref_clouds, 'ref_clouds')
+    n_shapes, n = ref_clouds.shape[0], ref_clouds.shape[1]
+    gen = generate_clouds(model, n_shapes, n if n_points is None else int(n_points), batch_size=batch_size, state=state)
+    gen = replace_nan_clouds(gen, generator=generator)
+    res = {}
+    if jsd:
+        res['jsd'] = JSD(gen, ref_clouds, clouds1_flag='gen', clouds2_flag='ref', warning=False) * 1e2
+    per_thr = generation_metrics(gen, ref_clouds, f1_threshold_lst, cd_option=cd, emd_option=emd, f1_option=f1)
+    for thr, m in per_thr.items():
+        if cd:
+            res.update(cd_mmds=m['lgan_mmd-CD'] * 1e4, cd_covs=m['lgan_cov-CD'] * 1e2, cd_1nns=m['1-NN-CD-acc'] * 1e2)
+        if emd:
+            res.update(emd_mmds=m['lgan_mmd-EMD'] * 1e2, emd_covs=m['lgan_cov-EMD'] * 1e2, emd_1nns=m['1-NN-EMD-acc'] * 1e2)
+        if f1:
+            res['f1_%.4f_mmds' % thr] = m['lgan_mmd-F1']
+            res['f1_%.4f_covs' % thr] = m['lgan_cov-F1'] * 1e2
+            res['f1_%.4f_1nns' % thr] = m['1-NN-F1-acc'] * 1e2
+    if not res:
+        return res
+    values = torch.stack([v.to(torch.float64) for v in res.values()]).tolist()       # the one read
+    return dict(zip(res.keys(), values))
 
 
 def pairwise_CD(clouds1, clouds2, bs=2048):
@@ -288,9 +349,35 @@ def KNN(Mxx, Mxy, Myy, k, sqrt=False):
     return float((pred == label).float().mean())
 
 
+def _on_device(x):
+    return torch.is_tensor(x) and x.is_cuda
+
+
+def _occupancy_warnings(clouds_flag, bound, n_out, n_nan):
+    """The reference's two messages (utils.py:47-54) from the kernel's two value counts."""
+    if n_out > 0:
+        print('{} clouds out of cube bounds: [-{}; {}]'.format(clouds_flag, bound, bound))
+    if n_nan > 0:
+        print('{} NaN values in point cloud tensors.'.format(n_nan))
+
+
+def _normalised(counts):
+    return counts.to(torch.float64) / counts.sum()
+
+
 def get_voxel_occ_dist(all_clouds, clouds_flag='gen', res=28, bound=0.5, bs=128, warning=True):
     """Occupancy histogram of all points over a res^3 grid of [-0.5, 0.5)^3, normalised (reference utils.py:45-79); points
-    outside the cube are dropped.  ``bs`` is accepted for signature compatibility (the reference chunks by it)."""
+    outside the cube are dropped.  ``bs`` is accepted for signature compatibility (the reference chunks by it).
+    A torch tensor on a HIP device takes the device path (metrics.voxel_occupancy: same rule, same counts) and the result is a
+    float64 DEVICE tensor, counts / counts.sum().  With warning=False that path synchronises nothing; with warning=True it reads the
+    kernel's two value counts once and prints the reference's messages.  One deviation: the reference prints the NaN message whatever
+    ``warning`` says; the device path prints it under warning=True only, because knowing the count is a read-back."""
+    if _on_device(all_clouds):
+        stats = torch.zeros(2, device=all_clouds.device, dtype=torch.int64) if warning else None
+        counts = _metrics.voxel_occupancy(all_clouds, res=res, bound=bound, stats=stats)
+        if warning:
+            _occupancy_warnings(clouds_flag, bound, *stats.tolist())
+        return _normalised(counts)
     if np.any(np.fabs(all_clouds) > bound) and warning:
         print('{} clouds out of cube bounds: [-{}; {}]'.format(clouds_flag, bound, bound))
     n_nans = np.isnan(all_clouds).sum()
@@ -306,7 +393,22 @@ def get_voxel_occ_dist(all_clouds, clouds_flag='gen', res=28, bound=0.5, bs=128,
 
 
 def JSD(clouds1, clouds2, clouds1_flag='gen', clouds2_flag='ref', warning=True):
-    """Jensen-Shannon divergence (base 2) between the two sets' occupancy histograms (reference utils.py:82-86)."""
-    d1 = get_voxel_occ_dist(clouds1, clouds_flag=clouds1_flag, warning=warning)
+    """Jensen-Shannon divergence (base 2) between the two sets' occupancy histograms (reference utils.py:82-86).
+    Two torch tensors on a HIP device take the device path: both histograms and the divergence are computed there
+    (metrics.voxel_occupancy, metrics.jsd_from_counts) and the result is a 0-d float64 DEVICE tensor; nothing is synchronised under
+    warning=False, and under warning=True the four value counts are read once for the reference's messages (get_voxel_occ_dist
+    names the one deviation).  A set without a single point inside the cube gives NaN, as the reference's 0 / 0 does."""
+    if _on_device(clouds1) or _on_device(clouds2):
+        if not (_on_device(clouds1) and _on_device(clouds2)) or clouds1.device != clouds2.device:
+            raise GwtfError('JSD: both cloud sets must be numpy arrays, or both tensors on one HIP device')
+        stats = torch.zeros(2, 2, device=clouds1.device, dtype=torch.int64) if warning else None
+        c1 = _metrics.voxel_occupancy(clouds1, stats=None if stats is None else stats[0])
+        c2 = _metrics.voxel_occupancy(clouds2, stats=None if stats is None else stats[1])
+        if warning:
+            (out1, nan1), (out2, nan2) = stats.tolist()
+            _occupancy_warnings(clouds1_flag, 0.5, out1, nan1)
+            _occupancy_warnings(clouds2_flag, 0.5, out2, nan2)
+        return _metrics.jsd_from_counts(c1, c2)
+    d1 =get_voxel_occ_dist(clouds1, clouds_flag=clouds1_flag, warning=warning)
     d2 = get_voxel_occ_dist(clouds2, clouds_flag=clouds2_flag, warning=warning)
     return entropy((d1 + d2).flatten() / 2.0, base=2) - 0.5 * (entropy(d1.flatten(), base=2) + entropy(d2.flatten(), base=2))

@@ -189,3 +189,69 @@ def f_score(predicted_clouds, true_clouds, threshold=0.001):
     precision = 100. * (rd < threshold).float().mean(1)
     recall = 100. * (ld < threshold).float().mean(1)
     return 2. * precision * recall / (precision + recall + 1e-7)
+
+
+# ---- occupancy histogram and Jensen-Shannon divergence (csrc/gwtf_occupancy.hip) ---------------------------------------------------
+OCC_MAX_RES = 32                      # the workgroup's private histogram of res^3 uint32 bins lives in LDS
+OCC_POINTS_PER_WORKGROUP = 8192       # kPointsPerGroup of csrc/gwtf_occupancy.hip: one workgroup per this many points, CUs at most
+
+
+def occupancy_edges(res):
+    """The reference's edge table (utils.py:56): the one statement of where a bin ends, for the host path and the kernel alike."""
+    return -0.5 + np.arange(res + 1) * (1. / res)
+
+
+def _int64_on(t, name, shape, device):
+    if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape) or t.dtype != torch.int64 or t.device != device or not t.is_contiguous():
+        raise GwtfError(f'{name} must be a contiguous int64 tensor of shape {tuple(shape)} on {device}')
+    return t
+
+
+def voxel_occupancy(clouds, res=28, bound=0.5, out=None, stats=None):
+    """How many points of ``clouds`` ((..., 3) float32, contiguous, on a HIP device) fall into each cell of the res^3 grid over
+    [-0.5, 0.5)^3 -> counts (res, res, res) int64 on the device: get_voxel_occ_dist's histogram before its normalisation (reference
+    utils.py:45-79), by the reference's rule -- coordinate x is in bin k iff edges[k] <= x < edges[k + 1], compared in float64; NaN,
+    +-inf and anything outside the cube have no bin, and a point counts when all three coordinates have one.
+    out: a (res, res, res) int64 tensor to ADD to (a set folded in batch by batch); stats: a (2,) int64 tensor to add
+    #{values with |x| > bound} and #{NaN values} to.  Integer counts: the same call gives the same bits.  Nothing is synchronised or
+    read back."""
+    if isinstance(res, bool) or not isinstance(res, (int, np.integer)) or not 1 <= res <= OCC_MAX_RES:
+        raise GwtfError(f'res must be an integer in 1..{OCC_MAX_RES}, got {res!r}')
+    if not torch.is_tensor(clouds) or clouds.dim() < 1 or clouds.shape[-1] != 3:
+        raise GwtfError(f'clouds must be a (..., 3) tensor, got {tuple(clouds.shape) if torch.is_tensor(clouds) else type(clouds)}')
+    ptr = _ptr(clouds, 'clouds')
+    n_points = clouds.numel() // 3
+    if n_points == 0:
+        raise GwtfError('empty point set')
+    if not float(bound) >= 0.0:
+        raise GwtfError(f'bound must be >= 0, got {bound!r}')
+    res, dev = int(res), clouds.device
+    if out is None:
+        out = torch.zeros(res, res, res, device=dev, dtype=torch.int64)
+    _int64_on(out, 'out', (res, res, res), dev)
+    if stats is not None:
+        _int64_on(stats, 'stats', (2,), dev)
+    a = _lib.OccupancyArgs(points=ptr, n_points=n_points, res=res, bound=float(bound), counts=out.data_ptr(),
+                           stats=None if stats is None else stats.data_ptr(), stream=_stream(clouds))
+    a.edges[:res + 1] = occupancy_edges(res).tolist()
+    with torch.cuda.device(dev):
+        check(_lib.lib().gwtf_voxel_occupancy(ctypes.addressof(a)))
+    return out
+
+
+def jsd_from_counts(c1, c2):
+    """Jensen-Shannon divergence (base 2) of two occupancy histograms given as int64 counts of equal size on a HIP device
+    (reference utils.py:82-86 on counts / counts.sum()) -> 0-d float64 device tensor.  float64 throughout and a fixed summation
+    order: the same counts give the same bits.  A histogram without a single count gives NaN (the reference's 0 / 0).  Nothing is
+    synchronised or read back."""
+    for t, name in ((c1, 'c1'), (c2, 'c2')):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise GwtfError(f'{name} must live on a HIP device; there is no CPU path')
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise GwtfError(f'{name} must be a contiguous int64 tensor')
+    if c1.numel() != c2.numel() or c1.device != c2.device or not 1 <= c1.numel() < 2 ** 31:
+        raise GwtfError(f'the histograms must have the same number of bins on one device: got {tuple(c1.shape)} and {tuple(c2.shape)}')
+    out = torch.empty((), device=c1.device, dtype=torch.float64)
+    with torch.cuda.device(c1.device):
+        check(_lib.lib().gwtf_jsd_counts(c1.data_ptr(), c2.data_ptr(), c1.numel(), out.data_ptr(), _stream(c1)))
+    return out

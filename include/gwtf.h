@@ -6,7 +6,8 @@
  *   - returns 0 on success, otherwise a hipError_t value (or GWTF_E_* below); never throws;
  *   - all pointers are DEVICE pointers to contiguous fp32 (int32 where stated) buffers owned by
  *     the caller; the library allocates nothing and keeps NO mutable global state (no tuning switches, no environment
- *     variables: what a call does is a function of its arguments -- see GWTF_TUNE_* for the per-call tuning word);
+ *     variables: what a call does is a function of its arguments -- see GWTF_TUNE_* for the per-call tuning word; the one thing
+ *     remembered between calls changes no result: gwtf_voxel_occupancy notes per device that its kernel's LDS limit is raised);
  *   - work is enqueued on `stream` (a hipStream_t passed as void*) and returns immediately:
  *     no internal streams, events or synchronisation (same convention as the reference's own
  *     native ops, lib/metrics/pytorch_structural_losses/src/structural_loss.cpp:35);
@@ -825,6 +826,38 @@ int gwtf_norm2d_forward_sums(const GwtfNorm2dArgs* args, double* sums);
 int gwtf_norm2d_forward_apply(const GwtfNorm2dArgs* args, const double* sums, double count);
 int gwtf_norm2d_backward_sums(const GwtfNorm2dArgs* args, double* sums);
 int gwtf_norm2d_backward_apply(const GwtfNorm2dArgs* args, const double* sums, double count);
+
+/* Occupancy histogram and Jensen-Shannon divergence of the generation evaluation (csrc/gwtf_occupancy.hip; added without a version
+ * change, no existing record or signature moved): get_voxel_occ_dist and JSD of lib/networks/utils.py:45-86 without the copy of both
+ * cloud sets to the host.
+ * Binning rule, the reference's (utils.py:56-75), exactly: coordinate x (float32, widened to double) falls in bin k iff
+ * edges[k] <= x < edges[k + 1], compared in double; a point counts iff all three of its coordinates have a bin, and then adds one to
+ * counts[(kx * res + ky) * res + kz].  NaN, +-inf, x >= edges[res] and x < edges[0] have no bin.  The caller fills `edges` with the
+ * reference's table, -0.5 + arange(res + 1) * (1. / res) in float64: the table is the only statement of where a bin ends (a floor of
+ * (x + 0.5) * res is NOT the rule: most edges are no float32 value, and the float32 neighbours of an edge fall on the other side).
+ * stats counts VALUES, not points: stats[0] += #{|x| > bound} (NaN is not; +-inf is), stats[1] += #{NaN}: what the reference turns
+ * into its two warnings.  counts and stats are ADDED TO, never cleared: a set may be folded in call by call.  Integer atomics only:
+ * repeated calls give identical bits.  One persistent grid, one workgroup per 8192 points and one per CU at most, each with a private
+ * uint32 histogram of res^3 bins in LDS (131,072 B at res 32): the launcher raises the kernel's dynamic-LDS limit once per device and
+ * process -- the one piece of state this library keeps, it changes no result -- and returns GWTF_E_UNSUPPORTED without a launch when
+ * the runtime refuses that. */
+typedef struct GwtfOccupancyArgs {
+  const float* points;               /* [n_points][3], row-contiguous */
+  size_t n_points;
+  int res;                           /* 1..32 */
+  double edges[33];                  /* edges[0..res], strictly increasing */
+  float bound;
+  long long* counts;                 /* [res][res][res], added to */
+  long long* stats;                  /* [2] {values beyond bound, NaN values}, added to; or NULL */
+  void* stream;
+} GwtfOccupancyArgs;
+/* GWTF_E_BADARG without a launch: a NULL record, points or counts, n_points outside 1..2^32-1, res outside 1..32, a bound that is
+ * negative or NaN, edges[0..res] not strictly increasing. */
+int gwtf_voxel_occupancy(const GwtfOccupancyArgs* args);
+/* out[0] = H((p1 + p2) / 2) - (H(p1) + H(p2)) / 2 in bits (base 2), p = counts / sum(counts), H(p) = -sum p log2 p with a zero bin
+ * contributing zero (scipy.stats.entropy): one workgroup, float64 throughout, a fixed summation order.  A histogram whose sum is 0
+ * gives NaN, which is what the reference's 0 / 0 turns into.  GWTF_E_BADARG: a NULL pointer, bins < 1. */
+int gwtf_jsd_counts(const long long* c1, const long long* c2, int bins, double* out, void* stream);
 
 #ifdef __cplusplus
 }
