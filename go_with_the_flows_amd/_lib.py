@@ -114,6 +114,10 @@ _SIGNATURES = {
     'gwtf_norm2d_backward_apply': (ctypes.c_int, [ctypes.c_void_p, _c_fp, ctypes.c_double]),
     'gwtf_voxel_occupancy': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_jsd_counts': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_int, _c_fp, _c_fp]),
+    'gwtf_eval_frame': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_chamfer_paired_partials': (ctypes.c_int, [ctypes.c_int] * 2),
+    'gwtf_chamfer_paired': (ctypes.c_int, [_c_fp] * 3 + [ctypes.POINTER(ctypes.c_float)] + [ctypes.c_int] * 4 + [_c_fp]),
+    'gwtf_paired_finalise': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 5 + [_c_fp]),
 }
 
 PHASE_FWD_INIT, PHASE_FWD_A, PHASE_FWD_B, PHASE_BWD_A, PHASE_BWD_B, PHASE_BWD_C = range(6)
@@ -231,6 +235,13 @@ class OccupancyArgs(ctypes.Structure):
     """GwtfOccupancyArgs of include/gwtf.h (one set of points folded into an occupancy histogram): same field order."""
     _fields_ = [('points', ctypes.c_void_p), ('n_points', ctypes.c_size_t), ('res', ctypes.c_int), ('edges', ctypes.c_double * 33),
                 ('bound', ctypes.c_float), ('counts', ctypes.c_void_p), ('stats', ctypes.c_void_p), ('stream', ctypes.c_void_p)]
+
+
+class EvalFrameArgs(ctypes.Structure):
+    """GwtfEvalFrameArgs of include/gwtf.h (one batch of both cloud sets into the evaluation frame): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('gen', 'ref', 'orig_s', 'orig_c', 'gen_out', 'ref_out')] +
+                [(n, ctypes.c_int) for n in ('B', 'n', 'm', 'n_scale', 'translate', 'row_scale', 'row_shift')] +
+                [('scale', ctypes.c_float), ('shift', ctypes.c_double * 3), ('stream', ctypes.c_void_p)])
 
 
 EXPORTS = tuple(_SIGNATURES)

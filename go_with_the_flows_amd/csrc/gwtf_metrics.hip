@@ -174,6 +174,202 @@ __global__ __launch_bounds__(256) void chamfer_directed_kernel(const float* __re
   }
 }
 
+// The rescaling chain of the reference's evaluate (evaluating.py:100-120) fused with the layout change its metrics need: channel-major
+// (B,3,cnt) in, point-major (B,cnt,3) out, both sets in one launch (z = set).  One thread = one point: consecutive lanes read
+// consecutive floats of each channel row and a wave's 12-byte stores are one contiguous run.  Every statement of the reference is one
+// IEEE operation here, in its order (include/gwtf.h); the translation is added in double and rounded once, as torch rounds
+// float32 += float64.  Lanes past the end clamp their index (they load a valid point) and skip the store.
+__global__ __launch_bounds__(256) void eval_frame_kernel(GwtfEvalFrameArgs a) {
+  const bool second = blockIdx.z == 1;
+  const int cnt = second ? a.m : a.n;
+  if ((int)(blockIdx.x * 256) >= cnt) return;
+  const float* src = second ? a.ref : a.gen;
+  float* dst = second ? a.ref_out : a.gen_out;
+  const int i = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x, k = min(j, cnt - 1);
+  float v[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = src[((size_t)i * 3 + c) * cnt + k];
+  for (int s = 0; s < a.n_scale; ++s) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = v[c] * a.scale;
+  }
+  if (a.translate) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = (float)((double)v[c] + a.shift[c]);
+  }
+  if (a.row_scale) {
+    const float s = a.orig_s[i];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = v[c] * s;
+  }
+  if (a.row_shift) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = v[c] + a.orig_c[(size_t)i * 3 + c];
+  }
+  if (j < cnt) {
+    float* o = dst + ((size_t)i * cnt + j) * 3;
+    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
+  }
+}
+
+// Cloud i against cloud i, both directions: grid = (query chunks, pairs, 2 directions).  chamfer_directed_kernel's structure with one
+// target cloud per workgroup: PTS query points per thread in registers (chunk = 256 * PTS), the other cloud streamed through the LDS
+// tile and read by broadcast, minimum by fminf on the same sqdist3 -- each per-point minimum is nnd_kernel's dist1 / dist2 bit for
+// bit.  The workgroup reduces its chunk (lane: points in order; wave: shuffle tree; waves in order) and writes ONE partial of
+// kPairWords words -- float32 sum, kCdMaxThr int32 counts -- with plain stores; nothing is accumulated across workgroups.
+// PTS = 8 keeps the 8 evaluations per LDS read of the all-pairs kernel; PTS = 2 is for batches that would leave the device empty at
+// that chunk (B = 1 at 2500 points: 2 x 2 workgroups against 2 x 5).  Lanes past the end clamp their index and are left out of the sums.
+constexpr int kPairWords = 1 + kCdMaxThr;
+constexpr int kPairSmallChunk = 512;     // 256 threads x 2 points: the chunk the partial buffer is laid out for
+constexpr int kPairFillGroups = 256;     // PTS = 8 when its grid has at least this many workgroups (one per compute unit)
+
+template <int PTS>
+__global__ __launch_bounds__(256) void chamfer_paired_kernel(const float* __restrict__ xa, const float* __restrict__ xb,
+                                                             float* __restrict__ partials, CdThr thr, int n_thr, int B, int n,
+                                                             int m, int P) {
+  __shared__ float4 buf[kTile];
+  __shared__ float wsum[4];
+  __shared__ int wcnt[4][kCdMaxThr];
+  const bool rev = blockIdx.z == 1;
+  const int nq = rev ? m : n, nt = rev ? n : m;
+  const int c0 = blockIdx.x * (256 * PTS);
+  if (c0 >= nq) return;                                   // uniform: the grid is sized for the longer of the two sets
+  const int i = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* Q = (rev ? xb : xa) + (size_t)i * nq * 3;
+  const float* T = (rev ? xa : xb) + (size_t)i * nt * 3;
+  float2v ax[PTS / 2], ay[PTS / 2], az[PTS / 2], best[PTS / 2];
+#pragma unroll
+  for (int p = 0; p < PTS; ++p) {                         // point c0 + p * 256 + tid: consecutive lanes read consecutive points
+    const int k = min(c0 + p * 256 + tid, nq - 1);
+    ax[p / 2][p % 2] = Q[(size_t)k * 3 + 0];
+    ay[p / 2][p % 2] = Q[(size_t)k * 3 + 1];
+    az[p / 2][p % 2] = Q[(size_t)k * 3 + 2];
+  }
+#pragma unroll
+  for (int p = 0; p < PTS / 2; ++p) best[p] = float2v{3.4e38f, 3.4e38f};
+  for (int k0 = 0; k0 < nt; k0 += kTile) {
+    const int cn = min(kTile, nt - k0);
+    __syncthreads();
+    for (int s = tid; s < cn; s += 256) {
+      const float* b = T + (size_t)(k0 + s) * 3;
+      buf[s] = make_float4(b[0], b[1], b[2], 0.f);
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int k = 0; k < cn; ++k) {
+      const float4 b = buf[k];   // same address in every lane: LDS broadcast
+      const float2v bx = {b.x, b.x}, by = {b.y, b.y}, bz = {b.z, b.z};
+#pragma unroll
+      for (int p = 0; p < PTS / 2; ++p) {
+        const float2v d = sqdist3(bx, by, bz, ax[p], ay[p], az[p]);
+        best[p] = float2v{fminf(best[p][0], d[0]), fminf(best[p][1], d[1])};
+      }
+    }
+  }
+  float s = 0.f;
+  int c[kCdMaxThr];
+#pragma unroll
+  for (int h = 0; h < kCdMaxThr; ++h) c[h] = 0;
+#pragma unroll
+  for (int p = 0; p < PTS; ++p) {
+    const float d = best[p / 2][p % 2];
+    if (c0 + p * 256 + tid < nq) {
+      s += d;
+#pragma unroll
+      for (int h = 0; h < kCdMaxThr; ++h) c[h] += (h < n_thr && d < thr.v[h]) ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+#pragma unroll
+  for (int h = 0; h < kCdMaxThr; ++h) {
+    if (h < n_thr) {             // uniform
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) c[h] += __shfl_down(c[h], off);
+    }
+  }
+  if (lane == 0) {
+    wsum[wave] = s;
+#pragma unroll
+    for (int h = 0; h < kCdMaxThr; ++h) wcnt[wave][h] = c[h];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float* out = partials + (((size_t)blockIdx.z * B + i) * P + blockIdx.x) * kPairWords;
+    out[0] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+#pragma unroll
+    for (int h = 0; h < kCdMaxThr; ++h) out[1 + h] = __int_as_float(((wcnt[0][h] + wcnt[1][h]) + wcnt[2][h]) + wcnt[3][h]);
+  }
+}
+
+// Per-pair values from the partials (include/gwtf.h), one wave: lane l owns pairs l, l + 64, ...; each adds its pair's partials in
+// chunk order, evaluates the reference's float32 expressions, and keeps float64 running sums that a shuffle tree folds into the meter.
+__global__ __launch_bounds__(64) void paired_finalise_kernel(const float* __restrict__ partials, const float* __restrict__ emd_cost,
+                                                             float* __restrict__ cd, float* __restrict__ cdl, float* __restrict__ cdr,
+                                                             float* __restrict__ emd, float* __restrict__ f1, double* __restrict__ meter,
+                                                             int meter_head, int n_thr, int B, int n, int m, int P, int chunks_l,
+                                                             int chunks_r, float inv_n) {
+  const int lane = threadIdx.x;
+  double m_cd = 0.0, m_emd = 0.0, m_f1[kCdMaxThr];
+#pragma unroll
+  for (int h = 0; h < kCdMaxThr; ++h) m_f1[h] = 0.0;
+  for (int i = lane; i < B; i += 64) {
+    const float* L = partials + (size_t)i * P * kPairWords;
+    const float* R = partials + ((size_t)B + i) * P * kPairWords;
+    float sl = 0.f, sr = 0.f;
+    int cl[kCdMaxThr], cr[kCdMaxThr];
+#pragma unroll
+    for (int h = 0; h < kCdMaxThr; ++h) cl[h] = cr[h] = 0;
+    for (int k = 0; k < chunks_l; ++k) {
+      sl += L[(size_t)k * kPairWords];
+#pragma unroll
+      for (int h = 0; h < kCdMaxThr; ++h) cl[h] += __float_as_int(L[(size_t)k * kPairWords + 1 + h]);
+    }
+    for (int k = 0; k < chunks_r; ++k) {
+      sr += R[(size_t)k * kPairWords];
+#pragma unroll
+      for (int h = 0; h < kCdMaxThr; ++h) cr[h] += __float_as_int(R[(size_t)k * kPairWords + 1 + h]);
+    }
+    const float vl = sl / (float)n, vr = sr / (float)m, v = vl + vr;
+    if (cdl) cdl[i] = vl;
+    if (cdr) cdr[i] = vr;
+    if (cd) { cd[i] = v; m_cd += (double)v; }
+#pragma unroll
+    for (int h = 0; h < kCdMaxThr; ++h) {
+      if (h < n_thr) {
+        const float recall = 100.f * ((float)cl[h] / (float)n), precision = 100.f * ((float)cr[h] / (float)m);
+        const float f = ((2.f * precision) * recall) / ((precision + recall) + 1e-7f);
+        if (f1) f1[(size_t)h * B + i] = f;
+        m_f1[h] += (double)f;
+      }
+    }
+    if (emd_cost) {
+      const float e = emd_cost[i] * inv_n;
+      if (emd) emd[i] = e;
+      m_emd += (double)e;
+    }
+  }
+  if (!meter) return;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    m_cd += __shfl_down(m_cd, off);
+    m_emd += __shfl_down(m_emd, off);
+#pragma unroll
+    for (int h = 0; h < kCdMaxThr; ++h) m_f1[h] += __shfl_down(m_f1[h], off);
+  }
+  if (lane == 0) {
+    if (meter_head) {
+      meter[0] += (double)B;
+      if (cd) meter[1] += m_cd;
+      if (emd_cost) meter[2] += m_emd;
+    }
+#pragma unroll
+    for (int h = 0; h < kCdMaxThr; ++h) {
+      if (h < n_thr) meter[3 + h] += m_f1[h];
+    }
+  }
+}
+
 // reference nndistance.cu:129-148: grad_a[j] += 2 g_j (a_j - b_idx[j]); grad_b[idx[j]] -= the same.  z = direction.
 __global__ __launch_bounds__(256) void nnd_grad_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2,
                                                        const float* __restrict__ gd1, const int* __restrict__ idx1,
@@ -446,6 +642,55 @@ extern "C" int gwtf_chamfer_directed(const float* q, const float* t, float* sum,
   for (int h = 0; h < kCdMaxThr; ++h) th.v[h] = h < n_thr ? thr[h] : 0.f;
   hipLaunchKernelGGL(chamfer_directed_kernel, dim3((unsigned)(groups * nq)), dim3(256), 0, (hipStream_t)stream, q, t, sum, cnt, th,
                      n_thr, nq, nt, n, m);
+  return (int)hipGetLastError();
+}
+
+extern "C" int gwtf_eval_frame(const GwtfEvalFrameArgs* pa) {
+  if (!pa) return GWTF_E_BADARG;
+  const GwtfEvalFrameArgs& a = *pa;
+  if (!a.gen || !a.ref || !a.gen_out || !a.ref_out || a.B < 1 || a.B > 65535 || a.n < 1 || a.m < 1 || a.n_scale < 0 ||
+      a.n_scale > 2 || (a.row_scale && !a.orig_s) || (a.row_shift && !a.orig_c))
+    return GWTF_E_BADARG;
+  hipLaunchKernelGGL(eval_frame_kernel, dim3((max(a.n, a.m) + 255) / 256, a.B, 2), dim3(256), 0, (hipStream_t)a.stream, a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int gwtf_chamfer_paired_partials(int n, int m) {
+  return (n < 1 || m < 1) ? 0 : (max(n, m) + kPairSmallChunk - 1) / kPairSmallChunk;
+}
+
+// Query points per thread of a paired launch: a function of (B, n, m) alone, so gwtf_paired_finalise finds the chunks that were written.
+static int paired_points_per_thread(int B, int n, int m) {
+  const long long groups = (long long)((max(n, m) + kCdChunk - 1) / kCdChunk) * B * 2;
+  return groups >= kPairFillGroups ? kCdPts : kPairSmallChunk / 256;
+}
+
+extern "C" int gwtf_chamfer_paired(const float* a, const float* b, float* partials, const float* thr, int n_thr, int B, int n, int m,
+                                   void* stream) {
+  if (!a || !b || !partials || B < 1 || B > 65535 || n < 1 || m < 1 || n_thr < 0 || n_thr > kCdMaxThr || (n_thr > 0 && !thr))
+    return GWTF_E_BADARG;
+  CdThr th;
+  for (int h = 0; h < kCdMaxThr; ++h) th.v[h] = h < n_thr ? thr[h] : 0.f;
+  const int P = gwtf_chamfer_paired_partials(n, m), pts = paired_points_per_thread(B, n, m);
+  const dim3 grid((max(n, m) + 256 * pts - 1) / (256 * pts), B, 2);
+  if (pts == kCdPts)
+    hipLaunchKernelGGL(chamfer_paired_kernel<kCdPts>, grid, dim3(256), 0, (hipStream_t)stream, a, b, partials, th, n_thr, B, n, m, P);
+  else
+    hipLaunchKernelGGL(chamfer_paired_kernel<kPairSmallChunk / 256>, grid, dim3(256), 0, (hipStream_t)stream, a, b, partials, th, n_thr,
+                       B, n, m, P);
+  return (int)hipGetLastError();
+}
+
+extern "C" int gwtf_paired_finalise(const float* partials, const float* emd_cost, float* cd, float* cdl, float* cdr, float* emd,
+                                    float* f1, double* meter, int meter_head, int n_thr, int B, int n, int m, void* stream) {
+  if (!partials || B < 1 || B > 65535 || n < 1 || m < 1 || n_thr < 0 || n_thr > kCdMaxThr || (n_thr > 0 && !f1 && !meter) ||
+      (emd && !emd_cost))
+    return GWTF_E_BADARG;
+  const int chunk = 256 * paired_points_per_thread(B, n, m);
+  const float inv_n = (float)(1.0 / (double)n);
+  hipLaunchKernelGGL(paired_finalise_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partials, emd_cost, cd, cdl, cdr, emd, f1,
+                     meter, meter_head, n_thr, B, n, m, gwtf_chamfer_paired_partials(n, m), (n + chunk - 1) / chunk,
+                     (m + chunk - 1) / chunk, inv_n);
   return (int)hipGetLastError();
 }
 

@@ -10,6 +10,10 @@ pairwise_matrices / generation_metrics are the device-resident form of the gener
 all-pairs matrices come from metrics.chamfer_directed / metrics.emd_cost_pairs (no per-row host loop, a set against itself costs
 one directed pass, every F1 threshold comes out of the same pass), and the result dictionaries are those of compute_all_metrics.
 pairwise_CD / COV / MMD / KNN mirror lib/networks/utils.py:90-144.
+
+evaluate_generation / evaluate_autoencoding / evaluate_reconstruction are the three branches of the reference's evaluate
+(evaluating.py:13-266) in one call each, on the device; the two paired ones run on metrics.clouds_to_eval_frame and
+metrics.paired_metrics (cloud i against cloud i, one Chamfer pass for CD and every F1 threshold, sums kept on the device).
 """
 import numpy as np
 import torch
@@ -312,6 +316,81 @@ def evaluate_generation(model, ref_clouds, n_points=None, batch_size=64, f1_thre
         return res
     values = torch.stack([v.to(torch.float64) for v in res.values()]).tolist()       # the one read
     return dict(zip(res.keys(), values))
+
+
+def _device_batch(batch, needs_image):
+    """The tensors one batch of a device loader contributes, refused when they are not on a HIP device."""
+    if not isinstance(batch, dict) or 'cloud' not in batch or 'eval_cloud' not in batch:
+        raise GwtfError("every batch must be a dict with 'cloud' and 'eval_cloud' (DeviceCloudLoader / DeviceSVRLoader)")
+    if needs_image and 'image' not in batch:
+        raise GwtfError("evaluate_reconstruction needs batch['image'] (DeviceSVRLoader)")
+    for key in ('cloud', 'eval_cloud', 'image', 'orig_c', 'orig_s'):
+        t = batch.get(key)
+        if t is not None and not _on_device(t):
+            raise GwtfError(f"batch[{key!r}] must be a tensor on a HIP device; there is no CPU path")
+    return batch
+
+
+def _evaluate_paired(clouds_of, batches, needs_image, f1_threshold_lst, cd, emd, f1, frame):
+    """The loop both paired evaluations share: clouds from the model, the frame, the metrics, every sum kept on the device in one
+    meter; ONE read at the end -> ({'cd', 'emd', 'f1_%.4f'} float64 means over all pairs, unscaled; keys of disabled options left out)."""
+    thresholds = tuple(f1_threshold_lst) if f1 else ()
+    meter, n_batches = None, 0
+    for batch in batches:
+        batch = _device_batch(batch, needs_image)
+        ref = batch['eval_cloud']
+        if meter is None:
+            meter = _metrics.new_meter(len(thresholds), ref.device)
+        gen = clouds_of(batch)
+        gen_f, ref_f = _metrics.clouds_to_eval_frame(gen, ref, frame, orig_s=batch.get('orig_s'), orig_c=batch.get('orig_c'))
+        _metrics.paired_metrics(gen_f, ref_f, thresholds, cd=cd, emd=emd, meter=meter)
+        n_batches += 1
+    if n_batches == 0:
+        raise GwtfError('no batches: the iterable is empty')
+    sums = meter.tolist()                                                            # the one read
+    count, res = sums[0], {}
+    if cd:
+        res['cd'] = sums[1] / count
+    if emd:
+        res['emd'] = sums[2] / count
+    for h, thr in enumerate(thresholds):
+        res['f1_%.4f' % thr] = sums[_metrics.METER_HEAD + h] / count
+    return res
+
+
+@torch.no_grad()
+def evaluate_autoencoding(model, batches, n_points, f1_threshold_lst=(0.0001,), cd=True, emd=True, f1=True, frame=None, state=None):
+    """The autoencoding branch of the reference's evaluate (evaluating.py:80-120, 167-189) in one call, on the device.  ``batches``: any
+    iterable of device dicts as DeviceCloudLoader yields them ('cloud', 'eval_cloud', optionally 'orig_c', 'orig_s'; a ragged last
+    batch is fine).  Per batch: model.autoencode_many(batch['cloud'], n_points, state=state), metrics.clouds_to_eval_frame against
+    batch['eval_cloud'] (``frame``: metrics.EvalFrame, None: no rescaling), metrics.paired_metrics into one device meter; nothing is
+    read back inside the loop and ONE read happens at the end.
+    -> the reference's `res`: 'cd' (x 1e4), 'emd' (x 1e2), 'f1_%.4f' per threshold (unscaled), Python floats; options that are off
+    leave their keys out.  Every value is the float64 mean over all pairs of the float32 per-pair values: what EMD_CD_F1's
+    reduced=True mean computes, up to its float32 rounding.  The batch's tensors are NOT modified (the reference scales p_clouds in
+    place, evaluating.py:104-120)."""
+    res = _evaluate_paired(lambda batch: model.autoencode_many(batch['cloud'], n_points, state=state), batches, False,
+                           f1_threshold_lst, cd, emd, f1, frame)
+    if cd:
+        res['cd'] *= 1e4
+    if emd:
+        res['emd'] *= 1e2
+    return res
+
+
+@torch.no_grad()
+def evaluate_reconstruction(model, batches, n_points, f1_threshold_lst=(0.0001,), cd=True, emd=True, f1=True, frame=None, state=None):
+    """The reconstruction branch of the reference's evaluate (evaluating.py:80-120, 138-157, 252-261) in one call, on the device.
+    ``batches``: any iterable of device dicts as DeviceSVRLoader yields them ('image', 'cloud', 'eval_cloud', optionally 'orig_c',
+    'orig_s'; a ragged last batch is fine).  Per batch: model.reconstruct_many(batch['image'], n_points, state=state), then the frame
+    and the metrics as in evaluate_autoencoding; one Chamfer pass instead of one per metric and threshold, no transposed copies, and
+    ONE read at the end instead of one per metric and batch.
+    -> {'cd', 'emd', 'f1_%.4f' per threshold}, all unscaled, Python floats; options that are off leave their keys out.
+    [res['cd'], res['emd']] is what the reference returns (`[CD.avg, EMD.avg]`), 'f1_%.4f' what it prints.  Every value is the
+    float64 mean over all pairs: what the reference's batch-weighted AverageMeter of float32 batch means computes, up to rounding.
+    The batch's tensors are NOT modified (the reference scales p_clouds in place)."""
+    return _evaluate_paired(lambda batch: model.reconstruct_many(batch['image'], n_points, state=state), batches, True,
+                            f1_threshold_lst, cd, emd, f1, frame)
 
 
 def pairwise_CD(clouds1, clouds2, bs=2048):

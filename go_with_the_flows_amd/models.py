@@ -432,6 +432,21 @@ class Flow_Mixture_Model(Local_Cond_RNVP_MC_Global_RNVP_VAE):
             return out, (work['labels'] + 1).float()
         return out
 
+    @torch.no_grad()
+    def autoencode_many(self, g_clouds, n_points, return_labels=False, state=None):
+        """S clouds (S, 3, N) -> S clouds of ``n_points`` points decoded from their own latent codes: the autoencoding twin of
+        Flow_Mixture_SVR_Model.reconstruct_many (the reference calls `model(...)` in 'autoencoding' mode batch by batch,
+        evaluating.py:93).  The codes are encode(...)['g_posterior_samples'], in this mode the posterior means (no draw).  With a
+        state (clouds.make_state) the decoder step is ``generate_many`` -- components and base samples drawn on the device from that
+        state, no host round trip -- and ``sample_many`` (np.random component draws, sample by sample) otherwise.
+        -> (S, 3, n_points)[, labels (S, n_points) in 1..K]."""
+        if self.mode != 'autoencoding':
+            raise GwtfError(f"autoencode_many needs a model in 'autoencoding' mode (model.mode / util_mode), got {self.mode!r}")
+        g = self.encode(g_clouds)['g_posterior_samples']
+        if state is not None:
+            return self.generate_many(g, n_points, return_labels, state=state)
+        return self.sample_many(g, n_points, return_labels)
+
     def _decode_partitioned_many(self, z0, g_samples, labels):
         """z0 (S, 3, n) base samples, labels (S, n) numpy: point i of sample s through component labels[s, i] -> (S, 3, n)."""
         S, _, n = z0.shape

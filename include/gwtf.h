@@ -859,6 +859,62 @@ int gwtf_voxel_occupancy(const GwtfOccupancyArgs* args);
  * gives NaN, which is what the reference's 0 / 0 turns into.  GWTF_E_BADARG: a NULL pointer, bins < 1. */
 int gwtf_jsd_counts(const long long* c1, const long long* c2, int bins, double* out, void* stream);
 
+/* Paired evaluation of the autoencoding and reconstruction branches (csrc/gwtf_metrics.hip; added without a version change, no
+ * existing record or signature moved): the rescaling chain of lib/networks/evaluating.py:100-120 fused with the layout change its
+ * metrics need, cloud i against cloud i in one Chamfer launch, and the per-pair values and running sums in one small launch.
+ *
+ * The frame.  gen [B][3][n] and ref [B][3][m] channel-major (what the model and the loaders produce) -> gen_out [B][n][3] and ref_out
+ * [B][m][3] point-major (what every metric kernel takes); one launch for both.  Every value goes through the reference's in-place
+ * statements in the reference's order, each rounded on its own as torch rounds it:
+ *   n_scale times   x = x * scale                       float32              (:103 and :107: one per evaluation flag that is on)
+ *   translate       x = float(double(x) + shift[c])     ONE rounding          (:111-113: the shift is a float64 tensor, torch adds in
+ *                                                                              float64 and rounds the sum to float32)
+ *   row_scale       x = x * orig_s[b]                   float32              (:116)
+ *   row_shift       x = x + orig_c[b][c]                float32              (:119)
+ * With every flag off the launch is a pure layout change; NaN and inf pass through like any other value. */
+typedef struct GwtfEvalFrameArgs {
+  const float* gen;                  /* [B][3][n] */
+  const float* ref;                  /* [B][3][m] */
+  const float* orig_s;               /* [B], read when row_scale */
+  const float* orig_c;               /* [B][3], read when row_shift */
+  float* gen_out;                    /* [B][n][3] */
+  float* ref_out;                    /* [B][m][3] */
+  int B, n, m;
+  int n_scale;                       /* 0..2 multiplications by `scale` */
+  int translate, row_scale, row_shift;
+  float scale;
+  double shift[3];
+  void* stream;
+} GwtfEvalFrameArgs;
+/* GWTF_E_BADARG without a launch: a NULL record, a NULL cloud pointer, B outside 1..65535, n or m < 1, n_scale outside 0..2,
+ * row_scale with a NULL orig_s, row_shift with a NULL orig_c. */
+int gwtf_eval_frame(const GwtfEvalFrameArgs* args);
+/* Chunks per (direction, pair) the partial buffer of gwtf_chamfer_paired is laid out for: ceil(max(n, m) / 512); 0 for sizes < 1. */
+int gwtf_chamfer_paired_partials(int n, int m);
+/* Cloud i of a [B][n][3] against cloud i of b [B][m][3], both directions in one launch, grid (query chunks, B, 2).  Direction 0: the
+ * points of a against b; direction 1: the points of b against a.  The per-point minimum is dist1 / dist2 of gwtf_nn_distance bit for
+ * bit.  Every workgroup writes ONE partial of 9 words at partials[((d * B + i) * P + chunk) * 9], P = gwtf_chamfer_paired_partials(n, m):
+ * word 0 the float32 sum of its chunk's minima, words 1..8 int32 counts of minima < thr[h], compared in float32 (thr: HOST array of
+ * n_thr <= 8 values read during the call, NULL allowed when n_thr == 0).  The chunk is 2048 query points when that fills the device
+ * and 512 otherwise, a function of (B, n, m) alone that gwtf_paired_finalise repeats; the order of every sum is fixed -- lane, wave
+ * shuffle tree, waves in order -- and nothing is accumulated across workgroups: the same call gives the same bits.
+ * GWTF_E_BADARG without a launch: a NULL pointer, B outside 1..65535, n or m < 1, n_thr outside 0..8. */
+int gwtf_chamfer_paired(const float* a, const float* b, float* partials, const float* thr, int n_thr, int B, int n, int m,
+                        void* stream);
+/* The per-pair values from the partials of gwtf_chamfer_paired on the same (B, n, m, n_thr), in float32 and in the reference's
+ * expressions; one wave, one thread per pair adding that pair's partials in chunk order.  Every output pointer may be NULL:
+ *   cdl[i] = sum_l / n, cdr[i] = sum_r / m, cd[i] = cdl + cdr                                  (evaluation_metrics.py:73-78)
+ *   f1[h][i] = 2 P R / (P + R + 1e-7), R = 100 (cnt_l[h] / n), P = 100 (cnt_r[h] / m)          (utils.py:38-42)
+ *   emd[i] = emd_cost[i] * float(1 / double(n))   -- what `match_cost(...) / float(n)` evaluates to on the device (the division by a
+ *            host scalar is carried out as a multiplication by its reciprocal); emd_cost: the [B] output of gwtf_emd_cost, or NULL
+ * meter (or NULL): float64 running sums ON THE DEVICE, added to and never cleared: meter[3 + h] += sum_i f1[h][i] for h < n_thr, and
+ * when meter_head is non-zero meter[0] += B, meter[1] += sum_i cd[i] (when cd is given), meter[2] += sum_i emd[i] (when emd_cost is
+ * given).  The float32 per-pair values are widened and added in float64: every lane its pairs in pair order, then a shuffle tree.
+ * GWTF_E_BADARG without a launch: NULL partials, B outside 1..65535, n or m < 1, n_thr outside 0..8, f1 NULL with n_thr > 0 and no
+ * meter, emd given without emd_cost. */
+int gwtf_paired_finalise(const float* partials, const float* emd_cost, float* cd, float* cdl, float* cdr, float* emd, float* f1,
+                         double* meter, int meter_head, int n_thr, int B, int n, int m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
