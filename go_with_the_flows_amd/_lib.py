@@ -112,6 +112,10 @@ _SIGNATURES = {
     'gwtf_norm2d_forward_apply': (ctypes.c_int, [ctypes.c_void_p, _c_fp, ctypes.c_double]),
     'gwtf_norm2d_backward_sums': (ctypes.c_int, [ctypes.c_void_p, _c_fp]),
     'gwtf_norm2d_backward_apply': (ctypes.c_int, [ctypes.c_void_p, _c_fp, ctypes.c_double]),
+    'gwtf_conv2d_plan': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t)]),
+    'gwtf_conv2d_forward': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_conv2d_backward_input': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_conv2d_backward_weight': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_voxel_occupancy': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_jsd_counts': (ctypes.c_int, [_c_fp, _c_fp, ctypes.c_int, _c_fp, _c_fp]),
     'gwtf_eval_frame': (ctypes.c_int, [ctypes.c_void_p]),
@@ -229,6 +233,15 @@ class Norm2dArgs(ctypes.Structure):
                                                 'partials', 'dy', 'dx', 'd_residual', 'dgamma', 'dbeta')] +
                 [(n, ctypes.c_int) for n in ('N', 'C', 'H', 'W', 'relu', 'pool')] +
                 [('eps', ctypes.c_float), ('momentum', ctypes.c_float), ('stream', ctypes.c_void_p)])
+
+
+CONV2D_FORWARD, CONV2D_BACKWARD_INPUT, CONV2D_BACKWARD_WEIGHT = range(3)      # GWTF_CONV2D_* of include/gwtf.h
+
+
+class Conv2dArgs(ctypes.Structure):
+    """GwtfConv2dArgs of include/gwtf.h (one convolution, any of its three passes): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('x', 'w', 'y', 'dy', 'dx', 'dw', 'work')] +
+                [(n, ctypes.c_int) for n in ('N', 'Cin', 'H', 'W', 'Cout', 'k', 'stride', 'pad')] + [('stream', ctypes.c_void_p)])
 
 
 class OccupancyArgs(ctypes.Structure):

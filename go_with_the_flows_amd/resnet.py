@@ -13,8 +13,11 @@ Two paths, the split the PointNet encoder had before its training kernels:
   library convolutions but runs every BatchNorm2d with the ReLU, residual add and stem max-pool behind it through the fused
   kernels of csrc/gwtf_norm2d.hip (norm2d.norm_act_2d), forward and backward; the head stays on the modules.  After
   ``nn.SyncBatchNorm.convert_sync_batchnorm`` in a data-parallel run the same path takes its batch statistics over the images of all
-  ranks (one all-reduce of the float64 sums per layer and direction; the head on the gathered rows).  Convolution backward in HIP
-  is not built.
+  ranks (one all-reduce of the float64 sums per layer and direction; the head on the gathered rows).  With ``ResNet.train_conv =
+  'hip'`` as well (default ``'library'``; it needs ``train_norm = 'hip'``) the 20 convolutions of that path run on
+  csrc/gwtf_conv2d.hip (conv2d.conv2d), forward, input gradient and weight gradient: no library call between the image and the
+  pooled features, exact fp32 products, no atomics.  It is off by default: DESIGN section 8 item 6 has the per-layer standing
+  against the library.  Convolutions have no collectives, so a data-parallel run needs nothing more.
 ``forward_torch`` runs the module graph on any device and dtype (the CPU float64 evaluation the tests compare against).
 An eval-mode call that the kernels cannot take (CPU tensor, dtype other than float32, channels other than 4, images under
 32 x 32) raises GwtfError: there is no fallback.
@@ -25,6 +28,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import GwtfError, _ptr, _stream, check
+from .conv2d import conv2d
 from .norm2d import norm_act_2d
 
 
@@ -57,12 +61,15 @@ class BasicBlock(nn.Module):
         return self.relu(y)
 
 
-def _conv(conv, x):
+def _conv(conv, x, how='library'):
+    if how == 'hip':
+        return conv2d(x, conv)
     return F.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups)
 
 
 class ResNet(nn.Module):
     train_norm = 'library'      # 'hip': train-mode BatchNorm2d (+ ReLU, residual, stem pool) on csrc/gwtf_norm2d.hip; not in state_dict
+    train_conv = 'library'      # 'hip': the convolutions of the train_norm = 'hip' path on csrc/gwtf_conv2d.hip; not in state_dict
 
     def __init__(self, block, layers, num_classes=1000, zero_init_residual=False, groups=1, width_per_group=64,
                  replace_stride_with_dilation=None, norm_layer=None):
@@ -129,17 +136,28 @@ class ResNet(nn.Module):
         return self.relu(self.fc_bn(self.fc(x)))
 
     def forward_train_hip(self, x):
-        """The train-mode module graph with library convolutions and the fused BatchNorm2d kernels; same parameters, buffers and
-        running-statistics updates as forward_torch in train mode."""
+        """The train-mode module graph with the fused BatchNorm2d kernels and the library's convolutions or, with train_conv =
+        'hip', those of csrc/gwtf_conv2d.hip; same parameters, buffers and running-statistics updates as forward_torch in train
+        mode."""
         if not self._hip_ok:
             raise GwtfError("train_norm='hip' covers resnet18 (BasicBlock x [2,2,2,2], BatchNorm2d) only")
-        x = norm_act_2d(_conv(self.conv1, x), self.bn1, pool=True)
+        how = self._train_conv()
+        x = norm_act_2d(_conv(self.conv1, x, how), self.bn1, pool=True)
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             for blk in layer:
-                y = norm_act_2d(_conv(blk.conv1, x), blk.bn1)
-                r = x if blk.downsample is None else norm_act_2d(_conv(blk.downsample[0], x), blk.downsample[1], relu=False)
-                x = norm_act_2d(_conv(blk.conv2, y), blk.bn2, residual=r)
+                y = norm_act_2d(_conv(blk.conv1, x, how), blk.bn1)
+                r = x if blk.downsample is None else norm_act_2d(_conv(blk.downsample[0], x, how), blk.downsample[1], relu=False)
+                x = norm_act_2d(_conv(blk.conv2, y, how), blk.bn2, residual=r)
         return self._head_train(torch.flatten(self.avgpool(x), 1))
+
+    def _train_conv(self):
+        """train_conv, checked against train_norm: the HIP convolutions exist on the fused-norm path only."""
+        if self.train_conv not in ('library', 'hip'):
+            raise GwtfError(f"train_conv must be 'library' or 'hip', got {self.train_conv!r}")
+        if self.train_conv == 'hip' and self.train_norm != 'hip':
+            raise GwtfError(f"train_conv='hip' needs train_norm='hip' (got train_norm={self.train_norm!r}): the HIP convolutions run "
+                            'inside forward_train_hip')
+        return self.train_conv
 
     def _head_train(self, x):
         """fc -> fc_bn -> ReLU on the pooled rows.  In a synchronised data-parallel run (fc_bn a SyncBatchNorm) every rank evaluates
@@ -261,6 +279,7 @@ class ResNet(nn.Module):
         if self._needs_graph(x):
             if self.train_norm not in ('library', 'hip'):
                 raise GwtfError(f"train_norm must be 'library' or 'hip', got {self.train_norm!r}")
+            self._train_conv()
             if self.train_norm == 'hip' and not self._hip_ok:
                 raise GwtfError("train_norm='hip' covers resnet18 (BasicBlock x [2,2,2,2], BatchNorm2d) only")
             if not x.is_cuda:

@@ -827,6 +827,41 @@ int gwtf_norm2d_forward_apply(const GwtfNorm2dArgs* args, const double* sums, do
 int gwtf_norm2d_backward_sums(const GwtfNorm2dArgs* args, double* sums);
 int gwtf_norm2d_backward_apply(const GwtfNorm2dArgs* args, const double* sums, double count);
 
+/* The convolutions of the image encoder in train mode, all three passes (csrc/gwtf_conv2d.hip; added without a version change, no
+ * existing record or signature moved).  Bias-free, dilation 1, groups 1, contiguous NCHW float32, w in torch's parameter layout:
+ *   forward          y[n][co][oy][ox]  = sum over (ci, ky, kx) of x[n][ci][oy * stride - pad + ky][ox * stride - pad + kx] * w[co][ci][ky][kx]
+ *   backward_input   dx[n][ci][iy][ix] = sum over (co, ky, kx) of dy[n][co][oy][ox] * w[co][ci][ky][kx] where that output position
+ *                    exists (gather form).  EVERY element of dx is written, the zeros at positions no output reads included; `work`
+ *                    receives w transposed to [Cin][Cout][k][k] first.
+ *   backward_weight  dw[co][ci][ky][kx] = sum over (n, oy, ox) of dy * x.  The pixels are split into `splits` ranges; with more than
+ *                    one, each writes a partial dw to `work` and a second launch adds them in the order 0 .. splits-1.
+ * Products are exact fp32 (v_mfma_f32_16x16x4_f32); a contraction runs as four independent chains combined pairwise.  No atomics:
+ * two calls give the same bits.  Ho = (H + 2 * pad - k) / stride + 1, Wo likewise.
+ * Accepted: k in {1, 3, 7}, stride in {1, 2}, pad = k / 2, Cout a multiple of 16, Cin a multiple of 16 or Cin = 4 with k = 7 (the
+ * stem); any N >= 1, H >= 1, W >= 1.  Everything else: GWTF_E_UNSUPPORTED. */
+#define GWTF_CONV2D_FORWARD 0
+#define GWTF_CONV2D_BACKWARD_INPUT 1
+#define GWTF_CONV2D_BACKWARD_WEIGHT 2
+typedef struct GwtfConv2dArgs {
+  const float* x;                    /* [N][Cin][H][W]: forward, backward_weight */
+  const float* w;                    /* [Cout][Cin][k][k]: forward, backward_input; 16-byte aligned */
+  float* y;                          /* [N][Cout][Ho][Wo]: forward */
+  const float* dy;                   /* as y: both backward passes */
+  float* dx;                         /* as x: backward_input */
+  float* dw;                         /* as w: backward_weight */
+  float* work;                       /* the planner's work_floats for the pass (16-byte aligned); may be NULL when that is 0 */
+  int N, Cin, H, W, Cout, k, stride, pad;
+  void* stream;
+} GwtfConv2dArgs;
+/* All validate on the host before any launch.  GWTF_E_BADARG: a NULL record, a NULL or misaligned pointer among those the pass uses,
+ * a size < 1, N > 65535, an element count of x, y or w near 2^31, an unknown pass.  The planner launches nothing and reads no
+ * pointer of the record: it returns the status the pass would give a record with its pointers set, and on success the number of
+ * splits (1 for forward and backward_input) and the floats of `work` the pass needs (0: none); either output may be NULL. */
+int gwtf_conv2d_plan(const GwtfConv2dArgs* args, int pass, int* splits, size_t* work_floats);
+int gwtf_conv2d_forward(const GwtfConv2dArgs* args);
+int gwtf_conv2d_backward_input(const GwtfConv2dArgs* args);
+int gwtf_conv2d_backward_weight(const GwtfConv2dArgs* args);
+
 /* Occupancy histogram and Jensen-Shannon divergence of the generation evaluation (csrc/gwtf_occupancy.hip; added without a version
  * change, no existing record or signature moved): get_voxel_occ_dist and JSD of lib/networks/utils.py:45-86 without the copy of both
  * cloud sets to the host.

@@ -18,11 +18,16 @@ initial state with the same injected reparameterisation noise: its four loss ter
     python tools/bench_svr_train.py --profile-encoder 20 --batches 128      # the image encoder alone (library forward + backward)
     python tools/bench_svr_train.py --encoder-norm library,hip --variants graphed --out profiles/r23_svr_norm.jsonl
     python tools/bench_svr_train.py --profile-encoder 20 --batches 128 --encoder-norm hip
+    python tools/bench_svr_train.py --encoder-norm hip --encoder-conv library,hip --variants graphed --out profiles/r27_svr_conv.jsonl
 
 --encoder-norm: the values of ResNet.train_norm to measure ('library': BatchNorm2d / ReLU / add / max-pool on the library modules;
 'hip': the fused kernels of csrc/gwtf_norm2d.hip).  With more than one value every variant is built once per value and all of them
 are alternated in the one call; the profile programs take the first value.  norm2d_byte_model gives the bytes the fused kernels
 must move per pass, from the shapes alone: kernel time from a trace divides into it.
+
+--encoder-conv: the values of ResNet.train_conv to measure ('library': F.conv2d; 'hip': csrc/gwtf_conv2d.hip, which needs
+--encoder-norm hip: a 'hip' convolution is paired with the 'hip' norm only).  Alternated in the one call like the norms; the record
+key of a variant on the HIP convolutions ends in '+conv'.
 
 The profile programs are the programs of two `rocprofv3 --kernel-trace --stats` runs; tools/svr_train_split.py turns their kernel_stats.csv
 files into the split of a step's kernel time between the image encoder's library kernels and everything else.
@@ -45,6 +50,7 @@ from go_with_the_flows_amd.training import GraphedTrainStep  # noqa: E402
 
 VARIANTS = ('list', 'fused', 'graphed')
 NORMS = ('library', 'hip')
+CONVS = ('library', 'hip')
 
 
 def norm2d_byte_model(B, H, W):
@@ -99,11 +105,12 @@ def make_optimizer(model, cfg):
 class Variant:
     """One way of taking a step, on its own copy of the model (same initial state) with its own optimiser."""
 
-    def __init__(self, kind, base_model, cfg, batch, noise=None, norm='library'):
-        self.kind, self.batch, self.norm = kind, batch, norm
-        self.key = kind if norm == 'library' else f'{kind}/{norm}'
+    def __init__(self, kind, base_model, cfg, batch, noise=None, norm='library', conv='library'):
+        self.kind, self.batch, self.norm, self.conv = kind, batch, norm, conv
+        self.key = (kind if norm == 'library' else f'{kind}/{norm}') + ('' if conv == 'library' else '+conv')
         self.model = copy.deepcopy(base_model)
         self.model.img_encoder.train_norm = norm
+        self.model.img_encoder.train_conv = conv
         if noise is not None:
             self.model.reparameterize = lambda mu, logvar: noise * torch.exp(0.5 * logvar) + mu
         self.crit = models.Flow_Mixture_Loss(**cfg)
@@ -143,6 +150,8 @@ def main():
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--variants', default=','.join(VARIANTS), help='comma-separated subset of list,fused,graphed')
     ap.add_argument('--encoder-norm', default='library', help='comma-separated subset of library,hip (ResNet.train_norm)')
+    ap.add_argument('--encoder-conv', default='library', help='comma-separated subset of library,hip (ResNet.train_conv); hip is '
+                                                              'measured with --encoder-norm hip only')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r21_svr_train.jsonl'))
     ap.add_argument('--profile-steps', type=int, default=0, metavar='N',
                     help='run N steps of the graphed variant at the first batch size and exit (the program of a kernel trace)')
@@ -154,6 +163,10 @@ def main():
     assert all(k in VARIANTS for k in kinds), kinds
     norms = [n for n in args.encoder_norm.split(',') if n]
     assert norms and all(n in NORMS for n in norms), norms
+    convs = [c for c in args.encoder_conv.split(',') if c]
+    assert convs and all(c in CONVS for c in convs), convs
+    paths = [(n, c) for n in norms for c in convs if c == 'library' or n == 'hip']
+    assert paths, "--encoder-conv hip needs --encoder-norm hip"
     assert torch.cuda.is_available(), 'bench_svr_train needs a HIP device'
     dev, cfg = 'cuda:0', config()
     n_points, (H, W) = cfg['cloud_size'], cfg['image_size']
@@ -179,16 +192,17 @@ def main():
         batch = (g, p, imgs)
         if args.profile_encoder:
             enc = base.img_encoder
-            enc.train_norm = norms[0]
+            enc.train_norm, enc.train_conv = paths[0]
             for _ in range(args.profile_encoder):
                 enc.zero_grad(set_to_none=True)
                 enc(imgs).square().mean().backward()
             torch.cuda.synchronize()
-            print(json.dumps({'bench': 'svr_encoder_profile', 'B': B, 'steps': args.profile_encoder, 'encoder_norm': norms[0],
+            print(json.dumps({'bench': 'svr_encoder_profile', 'B': B, 'steps': args.profile_encoder, 'encoder_norm': paths[0][0],
+                              'encoder_conv': paths[0][1],
                               'norm2d_bytes_per_pass': norm2d_byte_model(B, H, W)}), flush=True)
             return
         if args.profile_steps:
-            v = Variant('graphed', base, cfg, batch, norm=norms[0])
+            v = Variant('graphed', base, cfg, batch, norm=paths[0][0], conv=paths[0][1])
             for _ in range(args.profile_steps):
                 v.step()
             torch.cuda.synchronize()
@@ -197,12 +211,12 @@ def main():
         noise = torch.randn(B, cfg['g_latent_space_size'], generator=torch.Generator().manual_seed(2323)).to(dev)
         terms = {}
         for kind in kinds:                      # one step each from the same state with the same noise: the same four numbers
-            for norm in norms:
-                v = Variant(kind, base, cfg, batch, noise, norm)
+            for norm, conv in paths:
+                v = Variant(kind, base, cfg, batch, noise, norm, conv)
                 terms[v.key] = [float(t) for t in v.step()]
                 del v
         torch.cuda.empty_cache()
-        vs = [Variant(kind, base, cfg, batch, norm=norm) for kind in kinds for norm in norms]
+        vs = [Variant(kind, base, cfg, batch, norm=norm, conv=conv) for kind in kinds for norm, conv in paths]
         for v in vs:
             for _ in range(args.warmup):
                 v.step()
@@ -218,6 +232,12 @@ def main():
                                                round(max(ms['graphed']) / min(ms['graphed/hip']), 3))
             rec['hip_faster_beyond_spread'] = max(ms['graphed/hip']) < min(ms['graphed'])
             rec['hip_slower_beyond_spread'] = min(ms['graphed/hip']) > max(ms['graphed'])
+        if 'graphed/hip' in ms and 'graphed/hip+conv' in ms:       # both on the fused norm kernels; only the convolutions differ
+            lib, hip = ms['graphed/hip'], ms['graphed/hip+conv']
+            rec['encoder_conv'] = convs
+            rec['graphed_conv_library_over_hip'] = round(min(lib) / max(hip), 3), round(max(lib) / min(hip), 3)
+            rec['hip_conv_faster_beyond_spread'] = max(hip) < min(lib)
+            rec['hip_conv_slower_beyond_spread'] = min(hip) > max(lib)
         if 'list' in ms and 'graphed' in ms:
             rec['list_over_graphed'] = round(min(ms['list']) / max(ms['graphed']), 3), round(max(ms['list']) / min(ms['graphed']), 3)
             rec['graphed_faster_beyond_spread'] = max(ms['graphed']) < min(ms['list'])
