@@ -53,6 +53,12 @@ _SIGNATURES = {
     'gwtf_adam_chunk_elems': (ctypes.c_int, []),
     'gwtf_adam_step_table': (ctypes.c_int, [_c_fp] * 3 + [ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_double,
                                              ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, _c_fp]),
+    'gwtf_adam_hyper': (ctypes.c_int, [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    'gwtf_adam_step_table_dev': (ctypes.c_int, [_c_fp] * 3 + [ctypes.c_int, _c_fp, _c_fp, ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                                                 _c_fp]),
+    'gwtf_loop_begin': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_loop_detect': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_loop_commit': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_nn_distance': (ctypes.c_int, [_c_fp] * 6 + [ctypes.c_int] * 3 + [_c_fp]),
     'gwtf_nn_distance_grad': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 3 + [_c_fp]),
     'gwtf_approx_match': (ctypes.c_int, [_c_fp] * 4 + [ctypes.c_int] * 3 + [_c_fp]),
@@ -255,6 +261,22 @@ class EvalFrameArgs(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_void_p) for n in ('gen', 'ref', 'orig_s', 'orig_c', 'gen_out', 'ref_out')] +
                 [(n, ctypes.c_int) for n in ('B', 'n', 'm', 'n_scale', 'translate', 'row_scale', 'row_shift')] +
                 [('scale', ctypes.c_float), ('shift', ctypes.c_double * 3), ('stream', ctypes.c_void_p)])
+
+
+class LoopState(ctypes.Structure):
+    """GwtfLoopState of include/gwtf.h (the training loop's device-resident state, 160 bytes): same field order."""
+    _fields_ = ([('meters', ctypes.c_double * 12), ('hyper', ctypes.c_float * 8)] +
+                [(n, ctypes.c_int) for n in ('cursor', 'n_iters', 'adam_step', 'status', 'poisoned_at', 'skip', 'flag', 'reserved')])
+
+
+LOOP_POISONED, LOOP_EXHAUSTED = 1, 2                   # GwtfLoopState.status bits
+
+
+class LoopArgs(ctypes.Structure):
+    """GwtfLoopArgs of include/gwtf.h (the launches of the training loop's state kernels): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('state', 'plan', 'rows', 'mesh_rows', 'table')] + [('terms', ctypes.c_void_p * 4)] +
+                [(n, ctypes.c_int) for n in ('B', 'views', 'plan_len', 'table_rows', 'stop_on_inf', 'use_flag')] +
+                [('stream', ctypes.c_void_p)])
 
 
 EXPORTS = tuple(_SIGNATURES)

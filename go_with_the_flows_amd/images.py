@@ -23,6 +23,7 @@ from ._lib import GwtfError
 from .clouds import epoch_plan, make_state, sample_clouds
 
 GRAY_WEIGHTS = (0.299, 0.587, 0.114)            # AddGrayscale (image_transformations.py:41-43)
+HOST_STORE_IN_CAPTURE = 'a host-resident ImageStore copies every batch from the host and cannot be captured; keep the store on the device'
 
 
 def resize_table(n_src, n_dst):
@@ -205,7 +206,7 @@ def _stage_rows(store, rows, dev):
     host, before the pair is written again two batches later, so neither the copy nor a kernel on any stream can still be reading
     it.  The store keeps ONE pair of buffers, as large as the largest batch seen; smaller batches use their leading part."""
     if torch.cuda.is_current_stream_capturing():
-        raise GwtfError('a host-resident ImageStore copies every batch from the host and cannot be captured; keep the store on the device')
+        raise GwtfError(HOST_STORE_IN_CAPTURE)
     B = rows.numel()
     if int(rows.min()) < 0 or int(rows.max()) >= store.n_images:
         raise GwtfError(f'rows must lie in [0, {store.n_images}) for a host-resident store')

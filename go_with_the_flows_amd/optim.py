@@ -160,10 +160,36 @@ class LRUpdater:
         self.beta1 = kwargs['beta1']
         self.min_beta2, self.max_beta2 = kwargs['min_beta2'], kwargs['max_beta2']
 
-    def __call__(self, optimizer, epoch, iteration):
+    def values(self, epoch, iteration):
+        """(lr, (beta1, beta2)) of the step taken at (epoch, iteration): Python floats, what ``__call__`` writes into every group."""
         import math
         phase = ((epoch % self.cycle_length) * self.epoch_length + iteration) / (self.cycle_length * self.epoch_length)
         w = 0.5 * (1.0 + math.cos(math.pi * phase))
+        return self.min_lr + (self.max_lr - self.min_lr) * w, (self.beta1, self.min_beta2 + (self.max_beta2 - self.min_beta2) * w)
+
+    def __call__(self, optimizer, epoch, iteration):
+        lr, betas = self.values(epoch, iteration)
         for group in optimizer.param_groups:
-            group['lr'] = self.min_lr + (self.max_lr - self.min_lr) * w
-            group['betas'] = (self.beta1, self.min_beta2 + (self.max_beta2 - self.min_beta2) * w)
+            group['lr'] = lr
+            group['betas'] = betas
+
+    def table(self, epoch, first_iteration, n, first_step):
+        """(n, 8) float32 numpy: row i is the record gwtf_adam_hyper gives for the update taken at (epoch, first_iteration + i) with
+        Adam step count first_step + i -- the reference's order: scheduler(optimizer, epoch, iter + i) runs before the step, and
+        state['step'] += 1 before the bias corrections.  Host only; the resident training loop indexes it on the device, so the
+        schedule is bit-equal to this class driving ``Adam.step()`` by construction."""
+        return hyper_table([self.values(epoch, first_iteration + i) for i in range(int(n))], first_step)
+
+
+def hyper_table(lr_betas, first_step):
+    """(len, 8) float32 numpy of gwtf_adam_hyper records {lr, beta1, beta2, 1-beta1, 1-beta2, 1-beta1^t, sqrt(1-beta2^t), 0} for the
+    (lr, (beta1, beta2)) of consecutive updates, t = first_step + i: each entry formed in float64 and cast to float32 once, the
+    arithmetic of csrc/gwtf_adam.hip (Python's float ** int and math.sqrt are the C library's pow and sqrt)."""
+    import math
+    import numpy as np
+    first_step = int(first_step)
+    if first_step < 1:
+        raise ValueError('first_step is the 1-based count of the first update: it must be at least 1')
+    rows = [[lr, b1, b2, 1.0 - b1, 1.0 - b2, 1.0 - float(b1) ** (first_step + i), math.sqrt(1.0 - float(b2) ** (first_step + i)), 0.0]
+            for i, (lr, (b1, b2)) in enumerate(lr_betas)]
+    return np.asarray(rows, np.float64).reshape(len(rows), 8).astype(np.float32)

@@ -11,9 +11,16 @@ per rank.  Every exchange is inside it -- the packed BatchNorm-statistic all-red
 (dist.OverlappedGradients: one asynchronous all-reduce per decoder launched from inside the backward pass + one flat remainder)
 -- as RCCL kernels captured with the rest (RCCL collectives are stream-capturable); no host synchronisation anywhere in the
 step.  This replaces DistributedDataParallel's bucketed all-reduce (train_ae.py:153), whose hooks are host-driven.
+
+``ResidentTrainLoop`` captures the whole iteration of the reference's loop instead -- batch draw, forward, loss, backward, NaN guard,
+learning-rate schedule, optimiser and meters -- with the loop's state in device memory (csrc/gwtf_loop.hip); the host only replays.
 """
+import ctypes
+
+import numpy as np
 import torch
 
+from . import _lib
 from .dist import graph_capture as _graph_capture
 
 
@@ -102,3 +109,253 @@ class GraphedTrainStep:
         self.graph.replay()
         self.optimizer.step()
         return self.terms
+
+
+class ResidentTrainLoop:
+    """loop = ResidentTrainLoop(model, criterion, optimizer, loader, scheduler); loop.set_epoch(e); loop.run(len(loader)).
+
+    The reference's train() / train_svr() (lib/networks/training.py:12-100, 188-303) with the whole iteration on the device: ONE
+    graph replay draws the batch (``DeviceCloudLoader`` for ``Flow_Mixture_Model``, ``DeviceSVRLoader`` with a device-resident
+    ``ImageStore`` for ``Flow_Mixture_SVR_Model``), runs forward, loss and backward, tests the loss for NaN, looks up the cosine
+    schedule of lr and beta2, applies the Adam / AMSGrad update with that step's bias corrections and feeds the four AverageMeters.
+    The host only replays; ``meters()`` reads one 160-byte record (include/gwtf.h GwtfLoopState) when it wants to log.
+
+    Launch order inside the capture: gwtf_loop_begin (this iteration's rows of the epoch plan), sample_clouds, for SVR
+    transform_images, the body of ``GraphedTrainStep._fwd_bwd`` (gradient reducer included), gwtf_loop_commit (data-parallel: the
+    guard's flag is MAX-reduced over the ranks between gwtf_loop_detect and the commit, so that all ranks update or none does), one
+    gwtf_adam_step_table_dev per parameter group.
+
+    * ``scheduler``: an ``optim.LRUpdater`` (tabulated on the host per epoch, ``LRUpdater.table``, indexed on the device); None keeps
+      the groups' lr and betas, which must then agree over the groups.  Groups may differ in eps, weight_decay and amsgrad.
+    * The moments of every updated parameter are created HERE, as zeros with ``state['step'] = 0``, before the capture -- visible in
+      ``optimizer.state`` from construction on; a loaded optimiser state (``optimizer.load_state_dict``, then a new loop) is continued
+      from its step count.  ``meters()`` writes the device's step count back into ``optimizer.state[p]['step']``, so that
+      ``optimizer.state_dict()`` has the reference's format.  ``param_groups`` are not edited: the schedule lives in the table.
+    * Construction leaves no trace (``GraphedTrainStep``'s rule): its warm-up iterations restore BatchNorm buffers, the RNG state,
+      the loaders' sampler states and the loop state.
+    * A non-finite loss (NaN; with ``stop_on_inf`` an infinity too) poisons the loop: parameters, moments, step count and cursor stay
+      those from before that step (the reference's "Stopping without updating the net") and every later replay is a no-op for
+      them.  Replays beyond the end of the epoch are no-ops in the same sense.  BatchNorm running statistics and the sampler
+      states are NOT held back on such replays: the forward pass has run (the reference's failing pass moves them too, then exits).
+    * Refused: sparse, non-float32 or non-contiguous parameters, and unequal step counts.  A parameter that receives no gradient in
+      the warm-up iterations is left out of the update, and gets no optimiser state, as ``Adam.step()`` leaves it out (the mixture
+      models carry one); ``loop.parameters`` lists the ones the loop updates.
+    """
+
+    def __init__(self, model, criterion, optimizer, loader, scheduler=None, warmup=False, data_parallel=None, stop_on_inf=False,
+                 warmup_iters=2, average_gradients=True):
+        from .clouds import make_state
+        from .dist import OverlappedGradients, sharded
+        from .images import HOST_STORE_IN_CAPTURE
+        # (argument checks first: nothing below them may run on a refused call)
+        svr = hasattr(loader, 'image_store')
+        if svr != (getattr(model, 'img_encoder', None) is not None):
+            raise ValueError(f'{type(model).__name__} and {type(loader).__name__} do not go together: an image-conditioned model needs '
+                             'a DeviceSVRLoader, any other model a DeviceCloudLoader')
+        if svr and loader.image_store.device.type != 'cuda':
+            raise _lib.GwtfError(HOST_STORE_IN_CAPTURE)
+        if not loader.return_eval_cloud:
+            raise ValueError('the training step reads cloud and eval_cloud: the loader must return both')
+        if len(loader) < 1:
+            raise ValueError('the loader has no full batch')
+        groups = optimizer.param_groups
+        if scheduler is None and any((g['lr'], tuple(g['betas'])) != (groups[0]['lr'], tuple(groups[0]['betas'])) for g in groups):
+            raise ValueError('all parameter groups share one schedule table: without a scheduler their lr and betas must agree')
+        steps = set()
+        for group in groups:
+            for p in group['params']:
+                if p.is_sparse or (p.grad is not None and p.grad.is_sparse):
+                    raise RuntimeError('ResidentTrainLoop does not support sparse parameters or gradients')
+                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                    raise _lib.GwtfError('ResidentTrainLoop needs contiguous float32 parameters on a HIP device (no CPU path)')
+                if len(optimizer.state.get(p, {})):
+                    steps.add(int(optimizer.state[p]['step']))
+        if len(steps) > 1:
+            raise ValueError(f'the parameters carry unequal step counts {sorted(steps)}: one schedule table cannot serve them')
+        data_parallel = sharded() if data_parallel is None else data_parallel
+        if svr and data_parallel and getattr(model.img_encoder, 'train_norm', None) != 'hip':
+            raise NotImplementedError("multi-rank SVR training needs model.img_encoder.train_norm = 'hip'")
+        self.model, self.criterion, self.optimizer, self.loader, self.scheduler = model, criterion, optimizer, loader, scheduler
+        self.use_warmup_weights, self.data_parallel, self.stop_on_inf = warmup, bool(data_parallel), bool(stop_on_inf)
+        self.reducer = OverlappedGradients(model, average=average_gradients) if data_parallel else None
+        self._svr = svr
+        store = loader.mesh_store if svr else loader.store
+        dev = self.device = store.device
+        B, N = loader.batch_size, loader.cloud_size
+        self.n_iters = len(loader)
+        # ---- static buffers ----
+        self.g_static = torch.empty(B, 3, N, device=dev, dtype=torch.float32)
+        self.p_static = torch.empty(B, 3, N, device=dev, dtype=torch.float32)
+        self.i_static = None
+        if svr:
+            t, s = loader.image_transform, loader.image_store
+            self.i_static = torch.empty((B, t.C_out) + tuple(t.output_size(s.height, s.width)), device=dev, dtype=torch.float32)
+        self.rows = torch.zeros(B, dtype=torch.int32, device=dev)                   # item 0: valid until the first begin
+        self.mesh_rows = torch.zeros(B, dtype=torch.int32, device=dev) if svr else None
+        self.plan = torch.zeros(len(loader.index_plan()), dtype=torch.int32, device=dev)
+        self.table = torch.zeros(self.n_iters, 8, dtype=torch.float32, device=dev)
+        self.state = torch.zeros(ctypes.sizeof(_lib.LoopState) // 8, dtype=torch.int64, device=dev)     # one GwtfLoopState
+        self._meters_view = self.state.view(torch.float64)[:12]
+        self._ints = self.state.view(torch.int32)[32:40]        # cursor, n_iters, adam_step, status, poisoned_at, skip, flag, -
+        self._flag = self._ints[6:7]
+        if loader._state is None:                               # the seeds of the loaders' own __iter__
+            seed = loader.seed + 0x9E3779B97F4A7C15 * loader.rank
+            loader._state = make_state(seed, dev)
+            if svr:
+                loader._image_state = make_state(seed, dev)
+        self._step0 = steps.pop() if steps else 0
+        self._groups = []                                   # filled after the warm-up: it shows which parameters receive gradients
+        self._ints.copy_(torch.tensor([0, 0, self._step0, 0, -1, 1, 0, 0], dtype=torch.int32))     # n_iters = 0: warm-up replays are no-ops
+        # ---- warm-up (GraphedTrainStep's rule: no trace), then the capture ----
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        keep = [(b, b.detach().clone()) for b in model.buffers()]
+        keep += [(s, s.clone()) for s in (loader._state, getattr(loader, '_image_state', None)) if s is not None]
+        keep.append((self.state, self.state.clone()))
+        rng_cpu, rng_dev = torch.get_rng_state(), torch.cuda.get_rng_state(dev)
+        self.terms = None
+        with torch.cuda.stream(side):
+            for _ in range(warmup_iters):
+                self._args = None
+                self._iteration()
+            with_grad = {id(p) for group in groups for p in group['params'] if p.grad is not None}
+            with torch.no_grad():
+                for b, saved in keep:
+                    b.copy_(saved)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.set_rng_state(rng_cpu)
+        torch.cuda.set_rng_state(rng_dev, dev)
+        for mod in model.modules():
+            if hasattr(mod, 'invalidate_packed_weights'):
+                mod.invalidate_packed_weights()
+        self.terms = self._args = None
+        optimizer.zero_grad(set_to_none=True)
+        if not with_grad:
+            raise ValueError('no parameter of the optimiser receives a gradient from this model and loss')
+        if self._step0 > 0 and any(id(p) in with_grad and not len(optimizer.state.get(p, {})) for group in groups for p in group['params']):
+            raise ValueError(f'some parameters carry step count {self._step0}, others no optimiser state: one schedule table cannot serve them')
+        # ---- moments, and one pointer table per parameter group ----
+        chunk = _lib.lib().gwtf_adam_chunk_elems()
+        for group in groups:
+            ams, plist = bool(group['amsgrad']), [p for p in group['params'] if id(p) in with_grad]
+            if not plist:
+                continue
+            for p in plist:
+                st = optimizer.state[p]
+                if len(st) == 0:
+                    st['step'], st['exp_avg'], st['exp_avg_sq'] = 0, torch.zeros_like(p), torch.zeros_like(p)
+                if ams and 'max_exp_avg_sq' not in st:
+                    st['max_exp_avg_sq'] = torch.zeros_like(p)
+            sts = [optimizer.state[p] for p in plist]
+            rows = [[p.data_ptr(), s['exp_avg'].data_ptr(), s['exp_avg_sq'].data_ptr(), s['max_exp_avg_sq'].data_ptr() if ams else 0,
+                     p.numel()] for p, s in zip(plist, sts)]
+            cmap = [(i, c) for i, p in enumerate(plist) for c in range((p.numel() + chunk - 1) // chunk)]
+            self._groups.append({'plist': plist, 'ams': ams, 'eps': float(group['eps']), 'wd': float(group['weight_decay']),
+                                 'table': torch.tensor(rows, dtype=torch.int64).to(dev),
+                                 'cmap': torch.tensor(cmap, dtype=torch.int32).reshape(-1, 2).to(dev), 'n_chunks': len(cmap),
+                                 'gtab': torch.zeros(len(plist), dtype=torch.int64, device=dev)})
+        self.graph = torch.cuda.CUDAGraph()
+        with _graph_capture(self.graph):
+            self._iteration()
+        # gradient addresses are known only now: fill the device tables before the first replay
+        for g in self._groups:
+            grads = [p.grad for p in g['plist']]
+            if any(gr is None or gr.is_sparse or gr.dtype != torch.float32 or not gr.is_contiguous() for gr in grads):
+                raise _lib.GwtfError('the captured backward pass left a missing, sparse, non-float32 or non-contiguous gradient')
+            g['grads'] = grads                                   # (the graph's pool owns them; kept for the reader)
+            g['gtab'].copy_(torch.tensor([gr.data_ptr() for gr in grads], dtype=torch.int64))
+        self.parameters = [p for g in self._groups for p in g['plist']]     # the parameters the loop updates
+        self._host_step, self._host_cursor = self._step0, 0
+        self.epoch = None
+        torch.cuda.synchronize(dev)
+
+    # ---- the launches of one iteration (eager in the warm-up, then captured) ----
+    def _loop_args(self):
+        if self._args is None:
+            a = _lib.LoopArgs(state=self.state.data_ptr(), plan=self.plan.data_ptr(), rows=self.rows.data_ptr(),
+                              mesh_rows=None if self.mesh_rows is None else self.mesh_rows.data_ptr(), table=self.table.data_ptr(),
+                              B=self.loader.batch_size, views=self.loader.views if self._svr else 1, plan_len=self.plan.numel(),
+                              table_rows=self.table.shape[0], stop_on_inf=int(self.stop_on_inf), use_flag=int(self.data_parallel))
+            self._args = a
+        self._args.stream = torch.cuda.current_stream(self.device).cuda_stream
+        return self._args
+
+    def _iteration(self):
+        from .clouds import sample_clouds
+        from .dist import run as dist_run
+        L, loader, dev = _lib.lib(), self.loader, self.device
+        with torch.cuda.device(dev):
+            _lib.check(L.gwtf_loop_begin(ctypes.addressof(self._loop_args())))
+        out = {'cloud': self.g_static, 'eval_cloud': self.p_static}
+        if self._svr:
+            from .images import transform_images
+            sample_clouds(loader.mesh_store, self.mesh_rows, loader.cloud_size, True, loader.cloud_transform, loader._state, out=out)
+            transform_images(loader.image_store, self.rows, loader.image_transform, loader._image_state, out=self.i_static)
+        else:
+            sample_clouds(loader.store, self.rows, loader.cloud_size, True, loader.transform, loader._state, out=out)
+        self.terms = GraphedTrainStep._fwd_bwd(self)
+        if any(t.dtype != torch.float32 or not t.is_cuda for t in self.terms):
+            raise _lib.GwtfError('the criterion must return four float32 device scalars')
+        a = self._loop_args()
+        a.terms[:] = [t.data_ptr() for t in self.terms]
+        with torch.cuda.device(dev):
+            if self.data_parallel:
+                import torch.distributed as dist
+                _lib.check(L.gwtf_loop_detect(ctypes.addressof(a)))
+                dist_run(dist.all_reduce, self._flag, op=dist.ReduceOp.MAX)            # all ranks update, or none does
+            _lib.check(L.gwtf_loop_commit(ctypes.addressof(a)))
+            hyper, skip = self.state.data_ptr() + 96, self.state.data_ptr() + 128 + 20        # GwtfLoopState.hyper / .skip
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            for g in self._groups:
+                _lib.check(L.gwtf_adam_step_table_dev(g['table'].data_ptr(), g['gtab'].data_ptr(), g['cmap'].data_ptr(), g['n_chunks'],
+                                                      hyper, skip, g['eps'], g['wd'], int(g['ams']), stream))
+
+    # ---- the host's side ----
+    def set_epoch(self, epoch, first_iteration=0):
+        """Upload the epoch's plan and schedule table and set the cursor to ``first_iteration`` (the reference's resume ``iter``)."""
+        from .optim import hyper_table
+        epoch, first = int(epoch), int(first_iteration)
+        if not 0 <= first <= self.n_iters:
+            raise ValueError(f'first_iteration must lie in [0, {self.n_iters}]')
+        self.loader.set_epoch(epoch)
+        self.plan.copy_(torch.from_numpy(self.loader.index_plan().astype(np.int32)))
+        n = self.n_iters - first
+        if self.scheduler is not None:
+            rows = self.scheduler.table(epoch, first, n, self._host_step + 1)
+        else:
+            g0 = self.optimizer.param_groups[0]
+            rows = hyper_table([(g0['lr'], tuple(g0['betas']))] * n, self._host_step + 1)
+        table = np.zeros((self.n_iters, 8), np.float32)
+        table[first:] = rows
+        self.table.copy_(torch.from_numpy(table))
+        self._ints[:2].copy_(torch.tensor([first, self.n_iters], dtype=torch.int32))
+        self.epoch, self._host_cursor = epoch, first
+
+    def run(self, n):
+        """Replay n iterations.  Nothing is synchronised; replays beyond the end of the epoch (or after a poisoned step) are no-ops."""
+        if self.epoch is None:
+            raise RuntimeError('call set_epoch(epoch) before run(n)')
+        for _ in range(int(n)):
+            self.graph.replay()
+        done = max(0, min(int(n), self.n_iters - self._host_cursor))
+        self._host_cursor += done
+        self._host_step += done                                # (a poisoned loop stops counting on the device; nothing reads this then)
+        for g in self._groups:                                 # raw-pointer writes: tell the packed-weight caches
+            self.optimizer._bump_versions(g['plist'])
+
+    def meters(self, reset=False):
+        """One device-to-host copy of the record -> {'LB', 'PNLL', 'GNLL', 'GENT': (val, avg, sum, count), 'iteration', 'step',
+        'poisoned', 'poisoned_at', 'exhausted'}; the step count is written into ``optimizer.state``.  reset: zero the meters."""
+        rec = _lib.LoopState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+        if reset:
+            self._meters_view.zero_()
+        out = {}
+        for k, name in enumerate(('LB', 'PNLL', 'GNLL', 'GENT')):
+            val, total, count = rec.meters[3 * k:3 * k + 3]
+            out[name] = (val, total / count if count else 0.0, total, count)
+        out.update(iteration=rec.cursor, step=rec.adam_step, poisoned=bool(rec.status & _lib.LOOP_POISONED),
+                   poisoned_at=rec.poisoned_at, exhausted=bool(rec.status & _lib.LOOP_EXHAUSTED))
+        for p in self.parameters:
+            self.optimizer.state[p]['step'] = rec.adam_step
+        return out
+

@@ -341,6 +341,60 @@ int gwtf_adam_chunk_elems(void);
 int gwtf_adam_step_table(const unsigned long long* table, const unsigned long long* grads, const int* chunk_map, int n_chunks,
                          float lr, double beta1, double beta2, float eps, float weight_decay, int step, int amsgrad,
                          void* stream);
+/* The scalars of one update, on the host (launches nothing): out8 = {(float)lr, (float)beta1, (float)beta2, 1-beta1, 1-beta2,
+ * bc1 = 1 - beta1^step, bc2s = sqrt(1 - beta2^step), 0}, each formed in double and cast to float once -- the very values
+ * gwtf_adam_step and gwtf_adam_step_table hand their kernels (all three call one helper).  GWTF_E_BADARG: NULL out8, step < 1. */
+int gwtf_adam_hyper(double lr, double beta1, double beta2, int step, float* out8);
+/* gwtf_adam_step_table driven from DEVICE memory: the seven scalars are read from hyper[0..6] (a record of gwtf_adam_hyper), and every
+ * workgroup returns before it touches anything when *skip != 0.  The update of an element is the one of the two launches above.
+ * GWTF_E_BADARG without a launch: a NULL pointer, n_chunks < 0. */
+int gwtf_adam_step_table_dev(const unsigned long long* table, const unsigned long long* grads, const int* chunk_map, int n_chunks,
+                             const float* hyper, const int* skip, float eps, float weight_decay, int amsgrad, void* stream);
+
+/* The training loop's state ON THE DEVICE (csrc/gwtf_loop.hip): one replay of a captured graph is one iteration of the reference's
+ * train() (lib/networks/training.py:12-100) -- batch draw, forward, loss, backward, NaN guard, schedule, optimiser, meters -- and
+ * the host reads this record when it wants to log.  160 bytes, no padding.
+ *   meters: {val, sum, count} of LB, PNLL, GNLL, GENT, AverageMeter.update(v.item(), B) in float64
+ *   hyper:  the gwtf_adam_hyper record of the update in flight (what gwtf_adam_step_table_dev reads)
+ *   cursor: iteration within the epoch; n_iters: iterations of the epoch; adam_step: updates applied so far
+ *   status: bit 0 = poisoned (sticky: a non-finite loss was seen), bit 1 = exhausted (cursor >= n_iters at the last begin)
+ *   poisoned_at: cursor of the poisoned iteration (-1: none); skip: non-zero = the optimiser launches of this replay do nothing
+ *   flag: the guard's verdict on this replay's loss, between gwtf_loop_detect and gwtf_loop_commit (MAX-reduced over ranks) */
+typedef struct GwtfLoopState {
+  double meters[12];
+  float hyper[8];
+  int cursor, n_iters, adam_step, status, poisoned_at, skip, flag, reserved;
+} GwtfLoopState;
+/* The launches' arguments.  state: a GwtfLoopState in device memory.  plan [plan_len] int32: the epoch's item indices, uploaded once
+ * per epoch; rows [B] (and mesh_rows [B], or NULL: rows / views) the static index buffers the batch kernels read.  table
+ * [table_rows][8]: row i = the gwtf_adam_hyper record of iteration i of the epoch.  terms: the four float32 loss terms {loss, pnll,
+ * gnll, gent} of the replay.  use_flag: gwtf_loop_commit takes state->flag (written by gwtf_loop_detect, reduced by the caller)
+ * instead of testing the loss itself. */
+typedef struct GwtfLoopArgs {
+  void* state;
+  const int* plan;
+  int* rows;
+  int* mesh_rows;
+  const float* table;
+  const float* terms[4];
+  int B, views, plan_len, table_rows, stop_on_inf, use_flag;
+  void* stream;
+} GwtfLoopArgs;
+/* One workgroup each, plain stores only.
+ * gwtf_loop_begin: cursor < n_iters, (cursor + 1) B <= plan_len, cursor < table_rows and not poisoned: rows = plan[cursor B ..
+ *   (cursor + 1) B), mesh_rows = rows / views, the exhausted bit cleared.  Otherwise skip = 1, the exhausted bit set where the cursor
+ *   is the reason, and rows / mesh_rows left as they were (valid indices of the last batch).
+ * gwtf_loop_detect: flag = 1 when the loss is NaN -- bit test (bits & 0x7fffffff) > 0x7f800000, the library is built with
+ *   -fno-honor-nans -- or, with stop_on_inf, infinite (>=); else 0.
+ * gwtf_loop_commit: exhausted or already poisoned: skip = 1, nothing else moves.  A non-finite loss (use_flag: flag != 0): status |= 1,
+ *   poisoned_at = cursor, skip = 1, nothing else moves.  Otherwise hyper = table[cursor]; the four meters take val = the term
+ *   (LB: (pnll + gnll) - gent in float32, in that order, then widened), sum += val * B, count += B in float64; ++adam_step; ++cursor;
+ *   skip = 0.
+ * GWTF_E_BADARG without a launch: a NULL record, state, plan, rows (begin), table or term (commit), loss term (detect), B < 1,
+ * views < 1, plan_len < 0, table_rows < 0. */
+int gwtf_loop_begin(const GwtfLoopArgs* args);
+int gwtf_loop_detect(const GwtfLoopArgs* args);
+int gwtf_loop_commit(const GwtfLoopArgs* args);
 
 /* Structural losses between point sets -- the reference's only native code (CUDA extension
  * lib/metrics/pytorch_structural_losses, bound in pybind/bind.cpp:9-15).  Point sets are [b][n][3] / [b][m][3].
