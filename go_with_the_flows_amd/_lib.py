@@ -59,6 +59,7 @@ _SIGNATURES = {
     'gwtf_loop_begin': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_loop_detect': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_loop_commit': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_loop_eval_commit': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_nn_distance': (ctypes.c_int, [_c_fp] * 6 + [ctypes.c_int] * 3 + [_c_fp]),
     'gwtf_nn_distance_grad': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 3 + [_c_fp]),
     'gwtf_approx_match': (ctypes.c_int, [_c_fp] * 4 + [ctypes.c_int] * 3 + [_c_fp]),
@@ -364,14 +365,33 @@ def padded_width(f):
     return lib().gwtf_padded_width(f)
 
 
-def pack_weights(raw, C, f, G, train, pattern0=0, K=1):
+def gather_table(table, out, n_rows):
+    """gwtf_gather_table on the current stream: out[offset_i .. + numel_i) = source_i for the n_rows rows {pointer, offset, numel} of
+    the int64 device tensor `table` -- a raw arena from its parameter / buffer tensors, into storage of the caller's."""
+    with torch.cuda.device(out.device):
+        check(lib().gwtf_gather_table(table.data_ptr(), _ptr(out, 'raw'), int(n_rows), _stream(out)))
+    return out
+
+
+def _out_buffer(t, name, numel, like):
+    if t.numel() != numel or t.device != like.device:
+        raise GwtfError(f'{name} must hold {numel} floats on {like.device}, got {t.numel()} on {t.device}')
+    return t
+
+
+def pack_weights(raw, C, f, G, train, pattern0=0, K=1, out=None):
     """Packed stack / FiLM weights of K concatenated stacks of C couplings each (raw: K*C coupling records).  train (the train
-    pipeline's packing): the stack weights alone -- its FiLM heads read the raw arena in place; returns (pw, None)."""
+    pipeline's packing): the stack weights alone -- its FiLM heads read the raw arena in place; returns (pw, None).
+    out = (pw, pf): pack into these tensors (nothing is allocated: an in-place refresh of a persistent packing)."""
     L = lib()
     if raw.numel() != K * C * L.gwtf_raw_coupling_floats(f, G):
         raise GwtfError(f'raw arena has {raw.numel()} floats, expected {K * C * L.gwtf_raw_coupling_floats(f, G)}')
-    pw = torch.empty(K * C * L.gwtf_packed_w_coupling_floats(f), device=raw.device, dtype=torch.float32)
-    pf = None if train else torch.empty(K * C * L.gwtf_packed_film_coupling_floats(f, G), device=raw.device, dtype=torch.float32)
+    n_w, n_f = K * C * L.gwtf_packed_w_coupling_floats(f), K * C * L.gwtf_packed_film_coupling_floats(f, G)
+    if out is not None:
+        pw, pf = _out_buffer(out[0], 'packed_w', n_w, raw), None if train else _out_buffer(out[1], 'packed_film', n_f, raw)
+    else:
+        pw = torch.empty(n_w, device=raw.device, dtype=torch.float32)
+        pf = None if train else torch.empty(n_f, device=raw.device, dtype=torch.float32)
     with torch.cuda.device(raw.device):
         check(L.gwtf_pack_weights_k(_ptr(raw, 'raw'), _ptr(pw, 'packed_w'), _ptr(pf, 'packed_film'), K, C, f, G, int(pattern0),
                                     int(bool(train)), _stream(raw)))
@@ -406,14 +426,18 @@ class exact_fp32:
         return False
 
 
-def pack_weights_exact(raw, packed_film, C, f, G, pattern0=0, K=1):
-    """GwtfPackX records of K concatenated stacks of C couplings (the fp32 operands of the exact contraction body)."""
+def pack_weights_exact(raw, packed_film, C, f, G, pattern0=0, K=1, out=None):
+    """GwtfPackX records of K concatenated stacks of C couplings (the fp32 operands of the exact contraction body).
+    out: pack into this tensor (records + work list, `packed_x_floats`); its work list was zeroed when it was made and is left alone."""
     L = lib()
     n = K * C * L.gwtf_packed_x_coupling_floats(f)
     # behind the records: the work list of the flagging launch / re-run pair (include/gwtf.h), zero once -- the pair keeps it zero.
     # It lives and dies with the record it serves; like the record it belongs to one stream at a time.
-    px = torch.empty(n + WORKLIST_INTS, device=raw.device, dtype=torch.float32)
-    px[n:].zero_()
+    if out is not None:
+        px = _out_buffer(out, 'packed_x', n + WORKLIST_INTS, raw)
+    else:
+        px = torch.empty(n + WORKLIST_INTS, device=raw.device, dtype=torch.float32)
+        px[n:].zero_()
     with torch.cuda.device(raw.device):
         check(L.gwtf_pack_weights_exact(_ptr(raw, 'raw'), _ptr(packed_film, 'packed_film'), _ptr(px, 'packed_x'), K, C, f, G,
                                         int(pattern0), _stream(raw)))

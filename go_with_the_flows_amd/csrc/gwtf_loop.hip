@@ -5,6 +5,8 @@
 //   begin  : this iteration's rows of the epoch plan -> the static index buffers the batch kernels read
 //   detect : the guard's verdict on the loss -> state->flag (data-parallel runs MAX-reduce it before the commit)
 //   commit : poisoned / exhausted: skip the optimiser; otherwise the schedule row, the meters and the counters
+// The validation pass (eval(), training.py:103-184) keeps a record of its own and replaces the commit by
+//   eval_commit : poisoned / exhausted: nothing; a NaN or infinite loss poisons; otherwise the meters and the cursor
 // Nothing here is hot: every kernel is one workgroup and a handful of words.  All stores are plain global stores.
 #include <hip/hip_runtime.h>
 #include "../../include/gwtf.h"
@@ -23,6 +25,19 @@ __device__ __forceinline__ bool non_finite(float x, bool or_inf) {
 __device__ __forceinline__ bool runnable(const GwtfLoopState* s, const GwtfLoopArgs& a) {
   const int c = s->cursor;
   return c >= 0 && c < s->n_iters && c < a.table_rows && (long long)(c + 1) * a.B <= (long long)a.plan_len;
+}
+
+// AverageMeter.update(v.item(), B) of the four meters: val = v; sum += val * n; count += n  (float64, like the host's Python floats)
+__device__ __forceinline__ void feed_meters(GwtfLoopState* s, float pnll, float gnll, float gent, int B) {
+  const float lb = (pnll + gnll) - gent;                      // training.py:53 / :127, float32 in this order
+  const float vals[4] = {lb, pnll, gnll, gent};
+  const double n = (double)B;
+  for (int k = 0; k < 4; ++k) {
+    const double v = (double)vals[k];
+    s->meters[3 * k] = v;
+    s->meters[3 * k + 1] += v * n;
+    s->meters[3 * k + 2] += n;
+  }
 }
 
 __global__ __launch_bounds__(64) void loop_begin_kernel(const GwtfLoopArgs a) {
@@ -65,19 +80,27 @@ __global__ __launch_bounds__(64) void loop_commit_kernel(const GwtfLoopArgs a) {
   }
   const float* row = a.table + (size_t)cursor * 8;
   for (int i = 0; i < 8; ++i) s->hyper[i] = row[i];
-  // AverageMeter.update(v.item(), B): val = v; sum += val * n; count += n  (float64, like the host's Python floats)
-  const float lb = (pnll + gnll) - gent;                      // training.py:53, float32 in this order
-  const float vals[4] = {lb, pnll, gnll, gent};
-  const double n = (double)a.B;
-  for (int k = 0; k < 4; ++k) {
-    const double v = (double)vals[k];
-    s->meters[3 * k] = v;
-    s->meters[3 * k + 1] += v * n;
-    s->meters[3 * k + 2] += n;
-  }
+  feed_meters(s, pnll, gnll, gent, a.B);
   s->adam_step += 1;
   s->cursor = cursor + 1;
   s->skip = 0;
+}
+
+// The validation pass: eval() stops on NaN and on an infinity alike (training.py:130-135), whatever stop_on_inf says; no schedule row,
+// no optimiser: hyper, adam_step and skip stay as they are.
+__global__ __launch_bounds__(64) void loop_eval_commit_kernel(const GwtfLoopArgs a) {
+  if (threadIdx.x != 0) return;
+  GwtfLoopState* s = reinterpret_cast<GwtfLoopState*>(a.state);
+  if (!runnable(s, a) || (s->status & kPoisoned)) return;     // beyond the pass, or after a poisoned batch: nothing moves
+  const float loss = *a.terms[0], pnll = *a.terms[1], gnll = *a.terms[2], gent = *a.terms[3];
+  const int cursor = s->cursor;
+  if (non_finite(loss, true)) {
+    s->status |= kPoisoned;
+    s->poisoned_at = cursor;
+    return;
+  }
+  feed_meters(s, pnll, gnll, gent, a.B);
+  s->cursor = cursor + 1;
 }
 
 bool args_ok(const GwtfLoopArgs* a) {
@@ -103,5 +126,13 @@ extern "C" int gwtf_loop_commit(const GwtfLoopArgs* args) {
   for (int k = 0; k < 4; ++k)
     if (!args->terms[k]) return GWTF_E_BADARG;
   hipLaunchKernelGGL(loop_commit_kernel, dim3(1), dim3(64), 0, (hipStream_t)args->stream, *args);
+  return (int)hipGetLastError();
+}
+
+extern "C" int gwtf_loop_eval_commit(const GwtfLoopArgs* args) {
+  if (!args_ok(args)) return GWTF_E_BADARG;
+  for (int k = 0; k < 4; ++k)
+    if (!args->terms[k]) return GWTF_E_BADARG;
+  hipLaunchKernelGGL(loop_eval_commit_kernel, dim3(1), dim3(64), 0, (hipStream_t)args->stream, *args);
   return (int)hipGetLastError();
 }

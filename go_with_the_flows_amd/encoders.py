@@ -140,6 +140,51 @@ class _EncoderTrainFn(torch.autograd.Function):
         return (None, None, None, *grads)
 
 
+class PinnedEncoderWeights:
+    """The fused eval kernel's packing of a ``PointNetCloudEncoder`` in PERSISTENT device buffers: the raw arena (weights, BatchNorm
+    affine parameters and running statistics, gathered by one pointer-table launch) and the packing gwtf_encoder_pack makes of it.
+    ``refresh()`` is those two launches into the same storage -- no allocation, no version counter: capturable, and valid between
+    training steps that write parameters and running statistics through raw pointers.  While ``encoder.pin(self)`` holds,
+    ``encoder.packed()`` returns ``self.packed``.  The table describes the storage the tensors have now (``.to()`` needs a new set)."""
+
+    def __init__(self, enc):
+        L = _lib.lib()
+        src = enc._sources()
+        dev = src[0].device
+        if dev.type != 'cuda':
+            raise GwtfError('module parameters are on the CPU: packed weights live on a HIP device only (.cuda() the model first)')
+        self._widths = enc._widths_c()
+        size = L.gwtf_encoder_packed_floats(*self._widths)
+        if size == 0:
+            raise GwtfError(f'no encoder kernel was built for widths {enc._widths}: nothing to pin')
+        rows, off = [], 0
+        if any(t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() for t in src):
+            raise GwtfError('pinned eval weights need contiguous float32 parameters and buffers on one HIP device')
+        self._sources = [t.detach().view(-1) for t in src]         # (kept alive: the table's pointers)
+        for t in self._sources:
+            rows.append((t.data_ptr(), off, t.numel()))
+            off += t.numel()
+        if off != L.gwtf_encoder_raw_floats(*self._widths):
+            raise GwtfError('encoder raw arena size mismatch')
+        self.n_rows = len(rows)
+        self.table = torch.tensor(rows, dtype=torch.int64).to(dev)
+        self.raw = torch.empty(off, device=dev, dtype=torch.float32)
+        self.packed = torch.empty(size, device=dev, dtype=torch.float32)
+
+    def __reduce__(self):
+        """copy.deepcopy / pickle of a pinned encoder: the copy is not pinned."""
+        return (type(None), ())
+
+    def refresh(self):
+        _lib.gather_table(self.table, self.raw, self.n_rows)
+        with torch.cuda.device(self.raw.device):
+            check(_lib.lib().gwtf_encoder_pack(_ptr(self.raw, 'raw'), _ptr(self.packed, 'packed'), *self._widths, _stream(self.raw)))
+        return self
+
+    def buffers(self):
+        return {'encoder_raw': self.raw, 'encoder_packed': self.packed}
+
+
 class PointNetCloudEncoder(nn.Module):
     def __init__(self, init_n_channels, init_n_features, n_features):
         super().__init__()
@@ -189,7 +234,20 @@ class PointNetCloudEncoder(nn.Module):
     def _widths_c(self):
         return (ctypes.c_int * len(self._widths))(*self._widths), len(self._widths)
 
+    def pin(self, pinned=None):
+        """Pin packed() to a ``PinnedEncoderWeights`` (a new, refreshed one by default) and return it; kept through train() / eval() /
+        invalidate_packed_weights(), changed only by its refresh().  ``unpin()`` restores the version-keyed cache."""
+        pinned = PinnedEncoderWeights(self).refresh() if pinned is None else pinned
+        self.__dict__['_pinned'] = pinned
+        return pinned
+
+    def unpin(self):
+        self.__dict__['_pinned'] = None
+
     def packed(self):
+        pinned = self.__dict__.get('_pinned')
+        if pinned is not None:
+            return pinned.packed
         src = self._sources()
         stamp = tuple((t.data_ptr(), t._version) for t in src)
         if self._packed is None or stamp != self._stamp:

@@ -261,9 +261,7 @@ def _gather_stacked(engines):
         return torch.stack([torch.cat(flat) for flat in flats])
     tab.source = flats                    # tab.rows describe these lists
     out = torch.empty(len(engines), R, device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().gwtf_gather_table(table.data_ptr(), out.data_ptr(), len(rows), _lib._stream(out)))
-    return out
+    return _lib.gather_table(table, out, len(rows))
 
 
 def stacked_raw_arena(engines):
@@ -312,6 +310,9 @@ class StackEngine:
         self._flat_key, self._flat = None, None
         self._stack_tables = {}           # engine tuple -> _DeviceTable of the gathers this engine leads (_gather_stacked)
         self._bn = _BnTables()
+        # (pw, pf, px): this engine's slices of a pinned mixture packing (mixture.PinnedStackWeights) -- while set, packed() and
+        # packed_exact() hand these out whatever the version keys say; whoever pinned them refreshes them in place
+        self._pinned = None
 
     def __reduce__(self):
         """copy.deepcopy / pickle of a module that owns an engine: a FRESH engine over the (copied) couplings.  Every cache in
@@ -358,7 +359,10 @@ class StackEngine:
         return (stamp, sum(map(_VERSION, self._tracked)))
 
     def packed(self):
-        """The eval packing (running statistics folded) of the current parameters, cached until one of them changes."""
+        """The eval packing (running statistics folded) of the current parameters, cached until one of them changes.  Pinned
+        (mixture.PinnedStackWeights): the pinned buffers, as of their last refresh()."""
+        if self._pinned is not None:
+            return self._pinned[0], self._pinned[1]
         key = self._key()
         if key != self._cache_key:
             with torch.no_grad():
@@ -369,7 +373,10 @@ class StackEngine:
         return self._packed
 
     def packed_exact(self):
-        """The exact-fp32 operand record of the CURRENT eval packing (cached with it)."""
+        """The exact-fp32 operand record of the CURRENT eval packing (cached with it).  Pinned: this engine's part of the pinned
+        record, without a work list of its own (that one sits behind all K parts: the re-run of a single engine scans its tiles)."""
+        if self._pinned is not None:
+            return self._pinned[2]
         pw, pf = self.packed()
         if self._packed_x is None:
             with torch.no_grad():

@@ -12,6 +12,68 @@ from . import _lib
 from .flows import _needs_grad, _sharded, exact_record
 
 
+class PinnedStackWeights:
+    """Everything the eval density pass of a ``MixtureStack`` reads in packed form, in PERSISTENT device buffers: the (K, R) raw
+    arena, the K * C couplings' stack and FiLM packings, the exact-fp32 record with its work list behind it (zeroed once).
+
+    ``refresh()`` re-gathers the arena from the parameters and BatchNorm buffers (one pointer-table launch over all K engines) and
+    re-packs it into the same storage (gwtf_pack_weights_k and gwtf_pack_weights_exact with K stacks in one call each): three
+    launches, no allocation, no host-to-device copy, no look at a version counter -- so it can be captured in a hipGraph and replayed
+    between training steps that change parameters through raw pointers.  While ``stack.pin(self)`` holds, ``stack.packed()`` /
+    ``packed_exact()`` and the engines' return these buffers (the engines' as views of their K-th part).
+
+    The pointer table describes the storage the parameters have NOW: ``.to()`` / ``.cuda()`` / a module swap (SyncBatchNorm
+    conversion) need a new set.  In-place edits -- optimiser steps, ``load_state_dict``, running-statistic updates -- need a refresh."""
+
+    def __init__(self, stack):
+        L = _lib.lib()
+        engines = stack.engines
+        K, C, f, G = stack.K, stack.C, stack.f, stack.G
+        for e in engines:
+            e._refresh_flat()
+        dev = engines[0]._flat[0].device
+        if dev.type != 'cuda':
+            raise _lib.GwtfError('module parameters are on the CPU: packed weights live on a HIP device only (.cuda() the model first)')
+        R = C * L.gwtf_raw_coupling_floats(f, G)
+        rows = []
+        for k, e in enumerate(engines):
+            if sum(e._sizes) != R:
+                raise _lib.GwtfError(f'raw arena of component {k} has {sum(e._sizes)} floats, expected {R}')
+            off = k * R
+            for t, n in zip(e._flat, e._sizes):
+                if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+                    raise _lib.GwtfError('pinned eval weights need contiguous float32 parameters and buffers on one HIP device')
+                rows.append((t.data_ptr(), off, n))
+                off += n
+        self._sources = [e._flat for e in engines]          # (the detached views, padding zeros included: the table's pointers)
+        self.K, self.C, self.f, self.G, self.pattern0, self.n_rows = K, C, f, G, engines[0].pattern0, len(rows)
+        self.table = torch.tensor(rows, dtype=torch.int64).to(dev)
+        new = lambda n: torch.empty(n, device=dev, dtype=torch.float32)
+        self.raw = new(K * R).view(K, R)
+        self.pw, self.pf = new(K * C * L.gwtf_packed_w_coupling_floats(f)), new(K * C * L.gwtf_packed_film_coupling_floats(f, G))
+        self.nx = K * C * L.gwtf_packed_x_coupling_floats(f)
+        self.px = torch.zeros(self.nx + _lib.WORKLIST_INTS, device=dev, dtype=torch.float32)      # records | work list (stays zero)
+
+    def __reduce__(self):
+        """copy.deepcopy / pickle of a pinned model: the copy is not pinned (these buffers describe the original's storage)."""
+        return (type(None), ())
+
+    def refresh(self):
+        """Gather + pack the current parameters into the same storage: three launches on the current stream, nothing else."""
+        _lib.gather_table(self.table, self.raw, self.n_rows)
+        _lib.pack_weights(self.raw, self.C, self.f, self.G, False, self.pattern0, K=self.K, out=(self.pw, self.pf))
+        _lib.pack_weights_exact(self.raw, self.pf, self.C, self.f, self.G, self.pattern0, K=self.K, out=self.px)
+        return self
+
+    def buffers(self):
+        return {'raw': self.raw, 'packed_w': self.pw, 'packed_film': self.pf, 'packed_x': self.px}
+
+    def engine_views(self, k):
+        """(pw, pf, px) of component k: views into the K-stack buffers."""
+        part = lambda t, n: t[k * (n // self.K):(k + 1) * (n // self.K)]
+        return part(self.pw, self.pw.numel()), part(self.pf, self.pf.numel()), part(self.px, self.nx)
+
+
 class MixtureStack:
     """Batched driver for an ``nn.ModuleList`` of ``LocalCondRNVPDecoder`` with identical (n_flows, f, G)."""
 
@@ -26,12 +88,30 @@ class MixtureStack:
         self._cat_key, self._cat, self._keep = None, None, None
         self._catx_key, self._catx, self._keepx = None, None, None
         self._route_work = {}             # (S, n, K, P, device) -> routing scratch
+        self._pinned = None               # a PinnedStackWeights: packed() / packed_exact() return its buffers while it is set
 
     def __reduce__(self):
         """copy.deepcopy / pickle: a fresh stack over the (copied) decoders -- the caches here belong to the original's tensors."""
         return (MixtureStack, (self.decoders,))
 
+    def pin(self, pinned=None):
+        """Pin this stack (and its engines) to a ``PinnedStackWeights`` -- a new, refreshed one by default -- and return it: from now
+        on the packings read are that set's buffers, kept through train() / eval() / invalidate_packed_weights() and changed only by
+        its refresh().  ``unpin()`` restores the version-keyed caches."""
+        pinned = PinnedStackWeights(self).refresh() if pinned is None else pinned
+        self._pinned = pinned
+        for k, e in enumerate(self.engines):
+            e._pinned = pinned.engine_views(k)
+        return pinned
+
+    def unpin(self):
+        self._pinned = None
+        for e in self.engines:
+            e._pinned = None
+
     def packed(self):
+        if self._pinned is not None:
+            return self._pinned.pw, self._pinned.pf
         packs = [e.packed() for e in self.engines]
         key = tuple(id(pk[0]) for pk in packs)
         if key != self._cat_key:
@@ -41,6 +121,8 @@ class MixtureStack:
 
     def packed_exact(self):
         """The K components' exact-fp32 operand records, concatenated (re-run of out-of-range tiles, flows.range_rerun)."""
+        if self._pinned is not None:
+            return self._pinned.px
         self.packed()
         pxs = [e.packed_exact() for e in self.engines]
         key = tuple(id(x) for x in pxs)

@@ -196,6 +196,30 @@ class Local_Cond_RNVP_MC_Global_RNVP_VAE(nn.Module):
         return self.finish_encode(output_encoder), output_decoder, logits
 
 
+class EvalWeights:
+    """model.pin_eval_weights(): every packed-weight cache on the eval density path of a ``Flow_Mixture_Model`` in persistent device
+    buffers -- the K decoders' (mixture.PinnedStackWeights) and the cloud encoder's (encoders.PinnedEncoderWeights).  Every other
+    module of that path (Gaussian heads, prior flow, mixture-weight encoder, loss) reads parameters and running statistics in place
+    (DESIGN.md section 4b).  ``refresh()``: five launches into the same storage, no allocation, capturable."""
+
+    def __init__(self, model):
+        self.stack = model.mixture_stack().pin()
+        self.encoder = model.pc_encoder.pin()
+
+    def __reduce__(self):
+        """copy.deepcopy / pickle of a pinned model: the copy is not pinned."""
+        return (type(None), ())
+
+    def refresh(self):
+        self.stack.refresh()
+        self.encoder.refresh()
+        return self
+
+    def buffers(self):
+        """name -> pinned tensor (their data_ptr()s never change)."""
+        return {**self.stack.buffers(), **self.encoder.buffers()}
+
+
 class Flow_Mixture_Model(Local_Cond_RNVP_MC_Global_RNVP_VAE):
     """K point-flow decoders with per-shape mixture weights (reference flow_mixture.py:11-179)."""
 
@@ -316,6 +340,36 @@ class Flow_Mixture_Model(Local_Cond_RNVP_MC_Global_RNVP_VAE):
         if self._stack is None:
             self._stack = MixtureStack(self.pc_decoder)
         return self._stack
+
+    # -- eval packings pinned to persistent buffers (an eval graph that survives training: training.ResidentEvalLoop) ----------
+    eval_weights = None               # the EvalWeights this model is pinned to
+
+    def pin_eval_weights(self):
+        """Pin every packed-weight cache of the eval density path to persistent device buffers and return the set (EvalWeights; the
+        one in place when the model is pinned already).  While pinned, the eval pass reads those buffers whatever the version keys say
+        -- through model.train() / model.eval() / invalidate_packed_weights() -- and sees a parameter change only after
+        ``refresh()``.  The set describes the parameters' current storage: ``.to()`` / ``.cuda()`` unpin."""
+        if getattr(self, 'img_encoder', None) is not None:
+            raise NotImplementedError('an image-conditioned model cannot be pinned: the ResNet image encoder packs its weights on the '
+                                      'host (resnet.ResNet._pack_host)')
+        if self.eval_weights is None:
+            self.__dict__['eval_weights'] = EvalWeights(self)
+        return self.eval_weights
+
+    def unpin_eval_weights(self):
+        """Back to the version-keyed caches (which are dropped: they may predate what happened while the model was pinned)."""
+        if self.__dict__.get('eval_weights') is None:
+            return
+        self.__dict__['eval_weights'] = None
+        self.mixture_stack().unpin()
+        self.pc_encoder.unpin()
+        for mod in self.modules():
+            if hasattr(mod, 'invalidate_packed_weights'):
+                mod.invalidate_packed_weights()
+
+    def _apply(self, fn, *args, **kwargs):
+        self.unpin_eval_weights()         # .to() / .cuda() / .double(): the pinned pointer tables name storage that is replaced
+        return super()._apply(fn, *args, **kwargs)
 
     def forward_fused(self, g_input, p_input, warmup=False):
         """Training / density pass without the list API: -> (output_encoder, dec) with dec = {z, logdet (K,B,3,N); mu0, lv0

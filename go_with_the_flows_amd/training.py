@@ -14,6 +14,10 @@ step.  This replaces DistributedDataParallel's bucketed all-reduce (train_ae.py:
 
 ``ResidentTrainLoop`` captures the whole iteration of the reference's loop instead -- batch draw, forward, loss, backward, NaN guard,
 learning-rate schedule, optimiser and meters -- with the loop's state in device memory (csrc/gwtf_loop.hip); the host only replays.
+
+``ResidentEvalLoop`` is the other half of the reference's epoch (train_ae.py:165-166), eval(): the validation pass as graph replays
+between those of the training loop, on eval packings that are refreshed in place (models.EvalWeights); ``track_best``,
+``checkpoint`` and ``save_checkpoint`` are eval()'s best-model rule and the reference's checkpoint file.
 """
 import ctypes
 
@@ -359,3 +363,235 @@ class ResidentTrainLoop:
             self.optimizer.state[p]['step'] = rec.adam_step
         return out
 
+
+
+class _eval_flags:
+    """``model.eval()`` for the block, by the modules' flags alone, and the flags put back as they were: ``nn.Module.train`` would also
+    drop the version-keyed packed-weight caches and the data-parallel row layouts -- a trace a validation pass must not leave in a
+    model that is being trained (the pass itself reads the pinned packings)."""
+
+    def __init__(self, model):
+        self.mods = list(model.modules())
+
+    def __enter__(self):
+        self.flags = [m.training for m in self.mods]
+        for m in self.mods:
+            m.training = False
+
+    def __exit__(self, *exc):
+        for m, flag in zip(self.mods, self.flags):
+            m.training = flag
+        return False
+
+
+class ResidentEvalLoop:
+    """val = ResidentEvalLoop(model, criterion, val_loader); result = val.validate(epoch).
+
+    The reference's eval() (lib/networks/training.py:103-184: an eval-mode density pass over the validation part, the four
+    AverageMeters, a stop on a NaN or infinite loss) on the device, between the replays of a ``ResidentTrainLoop`` on the SAME model.
+    Two graphs, captured once:
+
+    * ``refresh``: ``model.pin_eval_weights().refresh()`` -- every packed-weight cache of the eval path re-gathered and re-packed into
+      persistent buffers (models.EvalWeights).  Replayed once at the start of a pass: the pass sees the
+      parameters and BatchNorm running statistics as training left them, however they were written.
+    * ``batch``: gwtf_loop_begin (this batch's rows of the plan) -> sample_clouds into static buffers -> ``forward_fused`` under eval
+      flags and no_grad (the K decoders in ONE stack launch) -> ``criterion.fused`` -> gwtf_loop_eval_commit (meters; poisoned on a
+      NaN or infinite loss, whatever follows is then a no-op).
+
+    ``validate`` uploads the plan, resets the record, replays ``refresh`` once and ``batch`` ``len(loader) - first_iteration`` times
+    (the reference's ``iter + i >= len(iterator)`` break) and reads the 160-byte record once; nothing in between synchronises.
+    Its pieces are public: ``begin(epoch)``, ``run(n)`` (``terms`` are then the static loss terms of the last batch), ``meters()``.
+
+    * The model stays pinned while the loop lives (``close()`` unpins a model the loop pinned itself); its train / eval flags, buffers
+      and the RNG states are after construction what they were before, as after ``GraphedTrainStep``'s.  The validation loader's
+      sampler state advances by one call per batch, as the loader's own iteration would; ``posterior='sample'`` draws from the CUDA
+      generator as eval() does.
+    * ``posterior='mean'``: the latent code is the posterior mean, no draw -- a deterministic validation loss the reference lacks.
+    * ``warmup``: the flag ``get_weights`` branches on; a pass with the other value captures a second batch graph on first use.
+    * Refused: image-conditioned models and ``DeviceSVRLoader`` (train_svr.py has no validation pass, and the ResNet encoder packs on
+      the host), more than one rank, a loader without ``eval_cloud`` or without a full batch.
+    """
+
+    def __init__(self, model, criterion, loader, warmup=False, posterior='sample'):
+        import torch.distributed as dist
+        from .clouds import make_state
+        # (argument checks first: nothing below them may run on a refused call, and they need no device)
+        if posterior not in ('sample', 'mean'):
+            raise ValueError(f"posterior must be 'sample' or 'mean', got {posterior!r}")
+        if getattr(model, 'img_encoder', None) is not None or hasattr(loader, 'image_store'):
+            raise NotImplementedError('ResidentEvalLoop covers the point-cloud autoencoder (train_ae.py): single-view reconstruction has no '
+                                      'validation pass in the reference (train_svr.py), and its ResNet encoder packs its weights on the host')
+        if not hasattr(model, 'pin_eval_weights'):
+            raise ValueError(f'{type(model).__name__} has no pinned eval packings: ResidentEvalLoop needs a Flow_Mixture_Model')
+        if (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1) or getattr(loader, 'world_size', 1) > 1:
+            raise NotImplementedError('ResidentEvalLoop runs on one rank: a validation pass over several ranks is not built')
+        if not loader.return_eval_cloud:
+            raise ValueError('the validation pass reads cloud and eval_cloud: the loader must return both')
+        if len(loader) < 1:
+            raise ValueError('the loader has no full batch')
+        dev = self.device = loader.store.device
+        if dev.type != 'cuda' or any(not p.is_cuda for p in model.parameters()):
+            raise _lib.GwtfError('ResidentEvalLoop needs the model and the mesh store on a HIP device (no CPU path)')
+        self.model, self.criterion, self.loader = model, criterion, loader
+        self.use_warmup_weights, self.posterior = bool(warmup), posterior
+        B, N = loader.batch_size, loader.cloud_size
+        self.n_iters = len(loader)
+        self.g_static = torch.empty(B, 3, N, device=dev, dtype=torch.float32)
+        self.p_static = torch.empty(B, 3, N, device=dev, dtype=torch.float32)
+        self.rows = torch.zeros(B, dtype=torch.int32, device=dev)                   # item 0: valid until the first begin
+        self.plan = torch.zeros(len(loader.index_plan()), dtype=torch.int32, device=dev)
+        self.state = torch.zeros(ctypes.sizeof(_lib.LoopState) // 8, dtype=torch.int64, device=dev)     # the pass's own GwtfLoopState
+        self._host_record(0, 0)                                                 # n_iters = 0: warm-up batches are no-ops for the record
+        if loader._state is None:                                               # the seed of the loader's own __iter__
+            loader._state = make_state(loader.seed + 0x9E3779B97F4A7C15 * loader.rank, dev)
+        self._owns_pin = model.eval_weights is None
+        self.weights = model.pin_eval_weights()
+        self._graphs, self._args, self._terms = {}, {}, {}
+        self.terms = None
+        self.refresh_graph = self._graph = None
+        self._capture(self.use_warmup_weights)
+        torch.cuda.synchronize(dev)
+
+    # ---- the launches of one batch (eager in the warm-up, then captured) ----
+    def _host_record(self, first, n_iters):
+        rec = _lib.LoopState(cursor=first, n_iters=n_iters, poisoned_at=-1)
+        self.state.copy_(torch.from_numpy(np.frombuffer(bytes(rec), dtype=np.int64).copy()))
+
+    def _batch(self, warmup):
+        from .clouds import sample_clouds
+        L, loader, dev = _lib.lib(), self.loader, self.device
+        a = self._args.get(warmup)
+        if a is None:
+            a = self._args[warmup] = _lib.LoopArgs(state=self.state.data_ptr(), plan=self.plan.data_ptr(), rows=self.rows.data_ptr(),
+                                                   mesh_rows=None, table=None, B=loader.batch_size, views=1, plan_len=self.plan.numel(),
+                                                   table_rows=self.n_iters, stop_on_inf=1, use_flag=0)
+        a.stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            _lib.check(L.gwtf_loop_begin(ctypes.addressof(a)))
+        sample_clouds(loader.store, self.rows, loader.cloud_size, True, loader.transform, loader._state,
+                      out={'cloud': self.g_static, 'eval_cloud': self.p_static})
+        enc, dec = self.model.forward_fused(self.g_static, self.p_static, warmup)
+        terms = tuple(t.detach() for t in self.criterion.fused(enc, dec))
+        if len(terms) != 4 or any(t.dtype != torch.float32 or not t.is_cuda for t in terms):
+            raise _lib.GwtfError('the criterion must return four float32 device scalars')
+        a.terms[:] = [t.data_ptr() for t in terms]
+        a.stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            _lib.check(L.gwtf_loop_eval_commit(ctypes.addressof(a)))
+        return terms
+
+    def _capture(self, warmup, warmup_iters=2):
+        """Capture the batch graph of this `warmup` flag (and, the first time, the refresh graph), leaving no trace."""
+        model, dev = self.model, self.device
+        keep = [(t, t.clone()) for t in (self.loader._state, self.state)]         # (an eval-mode pass writes no buffer of the model)
+        rng_cpu, rng_dev = torch.get_rng_state(), torch.cuda.get_rng_state(dev)
+        own = 'reparameterize' in model.__dict__
+        saved = model.__dict__.get('reparameterize')
+        if self.posterior == 'mean':
+            model.reparameterize = lambda mu, logvar: mu
+        try:
+            with _eval_flags(model), torch.no_grad():
+                side = torch.cuda.Stream(device=dev)
+                side.wait_stream(torch.cuda.current_stream(dev))
+                with torch.cuda.stream(side):
+                    for _ in range(warmup_iters):              # allocator + lazy initialisation outside the capture
+                        self.weights.refresh()
+                        self._batch(warmup)
+                    for t, was in keep:
+                        t.copy_(was)
+                torch.cuda.current_stream(dev).wait_stream(side)
+                torch.set_rng_state(rng_cpu)
+                torch.cuda.set_rng_state(rng_dev, dev)
+                if self.refresh_graph is None:
+                    self.refresh_graph = torch.cuda.CUDAGraph()
+                    with _graph_capture(self.refresh_graph):
+                        self.weights.refresh()
+                graph = torch.cuda.CUDAGraph()
+                with _graph_capture(graph):
+                    self._terms[warmup] = self._batch(warmup)
+                self._graphs[warmup] = graph
+                torch.set_rng_state(rng_cpu)
+                torch.cuda.set_rng_state(rng_dev, dev)
+        finally:
+            if own:
+                model.reparameterize = saved
+            else:
+                model.__dict__.pop('reparameterize', None)
+        return graph
+
+    # ---- the host's side ----
+    def validate(self, epoch, first_iteration=0, warmup=None):
+        """One validation pass -> ``meters()``'s dictionary.  first_iteration: the reference's resume ``iter`` (eval() runs
+        ``len(iterator) - iter`` batches); warmup: None = the constructor's flag.  (= begin, run to the end, meters.)"""
+        self.begin(epoch, first_iteration, warmup)
+        self.run(self.n_iters - int(first_iteration))
+        return self.meters()
+
+    def begin(self, epoch, first_iteration=0, warmup=None):
+        """Start a pass: upload the plan, reset the record (cursor = first_iteration, empty meters), replay ``refresh``."""
+        if self.model.eval_weights is not self.weights:
+            raise RuntimeError('the model is no longer pinned to this loop\'s eval packings (unpin_eval_weights(), .to() or close() '
+                               'since construction): build a new ResidentEvalLoop')
+        epoch, first = int(epoch), int(first_iteration)
+        if not 0 <= first <= self.n_iters:
+            raise ValueError(f'first_iteration must lie in [0, {self.n_iters}]')
+        warmup = self.use_warmup_weights if warmup is None else bool(warmup)
+        self._graph = self._graphs.get(warmup) or self._capture(warmup)
+        self.loader.set_epoch(epoch)
+        self.plan.copy_(torch.from_numpy(self.loader.index_plan().astype(np.int32)))
+        self._host_record(first, self.n_iters)
+        self.terms = self._terms[warmup]                       # the static loss terms of the batch replayed last
+        self.refresh_graph.replay()
+
+    def run(self, n):
+        """Replay n batches of the pass begun.  Nothing is synchronised; replays beyond its end, or after a poisoned batch, change
+        nothing in the record."""
+        if self._graph is None:
+            raise RuntimeError('call begin(epoch) before run(n)')
+        for _ in range(int(n)):
+            self._graph.replay()
+
+    def meters(self):
+        """One device-to-host copy of the record -> {'LB', 'PNLL', 'GNLL', 'GENT': (val, avg, sum, count), 'iteration', 'poisoned',
+        'poisoned_at'} of the last pass."""
+        rec = _lib.LoopState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+        out = {}
+        for k, name in enumerate(('LB', 'PNLL', 'GNLL', 'GENT')):
+            val, total, count = rec.meters[3 * k:3 * k + 3]
+            out[name] = (val, total / count if count else 0.0, total, count)
+        out.update(iteration=rec.cursor, poisoned=bool(rec.status & _lib.LOOP_POISONED), poisoned_at=rec.poisoned_at)
+        return out
+
+    def close(self):
+        """Drop the graphs; unpin the model if this loop pinned it."""
+        self._graphs, self._terms, self.refresh_graph, self._graph, self.terms = {}, {}, None, None, None
+        if self._owns_pin and self.model.eval_weights is self.weights:
+            self.model.unpin_eval_weights()
+
+
+# ---- best model and checkpoints (host side, once per epoch) ----------------------------------------------------------------------
+START_MIN_LOSS = 10000                                     # train_ae.py:162
+
+
+def track_best(result, min_loss=START_MIN_LOSS):
+    """eval()'s best-model rule (training.py:169-170) on ``ResidentEvalLoop.validate``'s result: -> (is_best, min_loss), is_best when
+    ``LB.avg < min_loss``; the new ``min_loss`` is then that average.  A poisoned pass is never the best (the reference exits)."""
+    avg = result['LB'][1]
+    if result.get('poisoned') or not avg < min_loss:
+        return False, min_loss
+    return True, avg
+
+
+def checkpoint(model, optimizer, epoch, iteration, loop=None):
+    """The reference's checkpoint dictionary (training.py:95-100, 178-183): {'epoch', 'iter', 'model_state', 'optimizer_state'}.
+    loop: the ``ResidentTrainLoop`` that drives the optimiser -- the device's step count is read into ``optimizer.state`` first
+    (``loop.meters()``).  It loads through train_ae.py:142-147; a new ``ResidentTrainLoop`` goes on with ``set_epoch(epoch, iter)``.
+    eval()'s best-model file takes ``epoch + 1, 0``; train()'s periodic one ``epoch, i + 1``."""
+    if loop is not None:
+        loop.meters()
+    return {'epoch': int(epoch), 'iter': int(iteration), 'model_state': model.state_dict(), 'optimizer_state': optimizer.state_dict()}
+
+
+def save_checkpoint(path, model, optimizer, epoch, iteration, loop=None):
+    """``torch.save`` of ``checkpoint(...)``: the reference's save_model."""
+    torch.save(checkpoint(model, optimizer, epoch, iteration, loop), path)

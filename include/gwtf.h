@@ -390,11 +390,17 @@ typedef struct GwtfLoopArgs {
  *   poisoned_at = cursor, skip = 1, nothing else moves.  Otherwise hyper = table[cursor]; the four meters take val = the term
  *   (LB: (pnll + gnll) - gent in float32, in that order, then widened), sum += val * B, count += B in float64; ++adam_step; ++cursor;
  *   skip = 0.
- * GWTF_E_BADARG without a launch: a NULL record, state, plan, rows (begin), table or term (commit), loss term (detect), B < 1,
- * views < 1, plan_len < 0, table_rows < 0. */
+ * gwtf_loop_eval_commit: the commit of the VALIDATION pass (eval(), lib/networks/training.py:103-184), on a record of its own (state)
+ *   that gwtf_loop_begin advances as it does the training loop's; table may be NULL, table_rows = n_iters.  Exhausted or already
+ *   poisoned: nothing moves.  A NaN or infinite loss -- (bits & 0x7fffffff) >= 0x7f800000, eval() stops on both, stop_on_inf and
+ *   use_flag are not read -- : status |= 1, poisoned_at = cursor, nothing else moves.  Otherwise the four meters take gwtf_loop_commit's
+ *   arithmetic, then ++cursor.  adam_step, hyper and skip are never written.
+ * GWTF_E_BADARG without a launch: a NULL record, state, plan, rows (begin), table (commit) or term (commit, eval_commit), loss term
+ * (detect), B < 1, views < 1, plan_len < 0, table_rows < 0. */
 int gwtf_loop_begin(const GwtfLoopArgs* args);
 int gwtf_loop_detect(const GwtfLoopArgs* args);
 int gwtf_loop_commit(const GwtfLoopArgs* args);
+int gwtf_loop_eval_commit(const GwtfLoopArgs* args);
 
 /* Structural losses between point sets -- the reference's only native code (CUDA extension
  * lib/metrics/pytorch_structural_losses, bound in pybind/bind.cpp:9-15).  Point sets are [b][n][3] / [b][m][3].
