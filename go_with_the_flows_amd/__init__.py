@@ -10,7 +10,7 @@ from .encoders import PointNetCloudEncoder, FeatureEncoder, WeightsEncoder
 from .prior import RealNVPFlow, RealNVPFlowCouple, GlobalRNVPDecoder, GaussianFlowNLL, GaussianEntropy
 from .models import Local_Cond_RNVP_MC_Global_RNVP_VAE, Flow_Mixture_Model, Flow_Mixture_SVR_Model, Flow_Mixture_Loss, FlowMixtureNLL
 from .resnet import ResNet, BasicBlock, resnet18
-from .clouds import MeshStore, CloudTransform, DeviceCloudLoader, sample_clouds, make_state
+from .clouds import MeshStore, CloudStore, CloudTransform, DeviceCloudLoader, sample_clouds, sample_stored_clouds, make_state
 from .images import ImageStore, ImageTransform, DeviceSVRLoader, transform_images
 from .metrics import EvalFrame, clouds_to_eval_frame, chamfer_paired, paired_metrics
 from .evaluation import evaluate_generation, evaluate_autoencoding, evaluate_reconstruction
@@ -21,6 +21,6 @@ __all__ = ['SharedDot', 'Swish', 'CondRealNVPFlow3D', 'CondRealNVPFlow3DTriple',
            'PointNetCloudEncoder', 'FeatureEncoder', 'WeightsEncoder', 'RealNVPFlow', 'RealNVPFlowCouple',
            'GlobalRNVPDecoder', 'GaussianFlowNLL', 'GaussianEntropy', 'Local_Cond_RNVP_MC_Global_RNVP_VAE',
            'Flow_Mixture_Model', 'Flow_Mixture_SVR_Model', 'Flow_Mixture_Loss', 'FlowMixtureNLL', 'ResNet', 'BasicBlock',
-           'resnet18', 'MeshStore', 'CloudTransform', 'DeviceCloudLoader', 'sample_clouds', 'make_state',
+           'resnet18', 'MeshStore', 'CloudStore', 'CloudTransform', 'DeviceCloudLoader', 'sample_clouds', 'sample_stored_clouds', 'make_state',
            'ImageStore', 'ImageTransform', 'DeviceSVRLoader', 'transform_images', 'EvalFrame', 'clouds_to_eval_frame',
            'chamfer_paired', 'paired_metrics', 'evaluate_generation', 'evaluate_autoencoding', 'evaluate_reconstruction']

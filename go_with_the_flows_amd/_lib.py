@@ -108,6 +108,8 @@ _SIGNATURES = {
     'gwtf_resnet_forward': (ctypes.c_int, [_c_fp] * 4 + [ctypes.c_int] * 5 + [_c_fp]),
     'gwtf_cloud_partials': (ctypes.c_int, [ctypes.c_int]),
     'gwtf_sample_clouds': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_sample_stored_clouds': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_perm_index': (ctypes.c_uint, [ctypes.POINTER(ctypes.c_uint), ctypes.c_uint, ctypes.c_uint]),
     'gwtf_route_tiles': (ctypes.c_int, [ctypes.c_int] * 3),
     'gwtf_mixture_route': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_stack_forward_routed': (ctypes.c_int, [ctypes.c_void_p]),
@@ -207,6 +209,16 @@ class CloudArgs(ctypes.Structure):
                     'cloud', 'eval_cloud', 'partials', 'state', 'words', 's1', 's2', 'normals')] +
                 [(n, ctypes.c_int) for n in ('B', 'M', 'n_shapes', 'rescale', 'recenter', 'translate', 'scale', 'noise', 'center',
                                              'tune')] +
+                [('shift', ctypes.c_float * 3), ('scale_div', ctypes.c_float), ('noise_scale', ctypes.c_float),
+                 ('stream', ctypes.c_void_p)])
+
+
+class StoredCloudArgs(ctypes.Structure):
+    """GwtfStoredCloudArgs of include/gwtf.h (one batch drawn from stored clouds): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('rows', 'points', 'bounds', 'orig_c', 'orig_s', 'cloud', 'eval_cloud', 'partials', 'state',
+                                                'index', 'normals')] +
+                [(n, ctypes.c_int) for n in ('B', 'M', 'n_shapes', 'rescale', 'recenter', 'translate', 'scale', 'noise', 'center',
+                                             'permute', 'tune')] +
                 [('shift', ctypes.c_float * 3), ('scale_div', ctypes.c_float), ('noise_scale', ctypes.c_float),
                  ('stream', ctypes.c_void_p)])
 

@@ -8,6 +8,9 @@
 
 Host work happens once, at construction: the per-face integer thresholds of every shape's area CDF, built with the reference's own
 arithmetic.  There is no CPU sampling path: sample_clouds on a CPU store raises.
+
+Data that are point clouds already go into a CloudStore, which stands wherever a MeshStore stands: a batch row then draws its
+points from the stored cloud without replacement (sample_stored_clouds), or reads them in stored order (permute=False).
 """
 import ctypes
 
@@ -175,15 +178,8 @@ def cloud_partials(M):
     return _lib.lib().gwtf_cloud_partials(int(M))
 
 
-def sample_clouds(store, rows, cloud_size, return_eval_cloud=True, transform=None, state=None, explicit=None, out=None):
-    """One batch: rows (B,) int32 shape indices on the store's device -> {'cloud': (B,3,cloud_size)[, 'eval_cloud'][, 'orig_c',
-    'orig_s']}, the keys and shapes of a collated reference batch.  Enqueued on the current stream; nothing waits for the device.
-
-    state: make_state(seed) (default: one the store keeps, seed 0).  explicit: {'words': (B,M) int32 bits of the uint32 face words,
-    's1', 's2': (B,M) float32, 'normals': (B,3,M) float32 when noise is on} replaces Philox (M = 2 * cloud_size with an eval cloud).
-    The scratch of a given (B, M) is allocated on the first call and kept on the store.  The returned tensors are fresh ones from
-    torch's allocator (which a graph capture records like any other); pass out={'cloud': ..., 'eval_cloud': ...} to write into
-    tensors of your own and allocate nothing at all."""
+def _prepare_batch(store, rows, cloud_size, return_eval_cloud, transform, state, out):
+    """The checks and buffers the two samplers share -> (transform, B, N, M, result dict, partials or None, state)."""
     if store.device.type != 'cuda':
         raise GwtfError(f'the store lives on {store.device}: sampling runs on a HIP device only, there is no CPU path')
     if rows.dtype != torch.int32 or rows.dim() != 1 or rows.device != store.device or not rows.is_contiguous():
@@ -215,15 +211,55 @@ def sample_clouds(store, rows, cloud_size, return_eval_cloud=True, transform=Non
         state = store._state
     if state.dtype != torch.int64 or state.numel() != 2 or state.device != dev:
         raise GwtfError('state must come from make_state(seed, device) on the store\'s device')
+    return t, B, N, M, res, partials, state
+
+
+def _explicit_pointers(explicit, fields, dev):
+    """Device addresses of the explicit draws named in fields ((key, shape, dtype), ...), each checked."""
     ex = {}
     if explicit is not None:
-        for k, shape, dt in (('words', (B, M), torch.int32), ('s1', (B, M), torch.float32), ('s2', (B, M), torch.float32)) + \
-                ((('normals', (B, 3, M), torch.float32),) if t.noise else ()):
+        for k, shape, dt in fields:
             v = explicit[k]
             if tuple(v.shape) != shape or v.dtype != dt or v.device != dev or not v.is_contiguous():
                 raise GwtfError(f'explicit[{k!r}] must be a contiguous {dt} tensor of shape {shape} on the store\'s device')
             ex[k] = v.data_ptr()
-    ptr = lambda x: None if x is None else x.data_ptr()
+    return ex
+
+
+def _with_original_frame(store, rows, res):
+    if store.orig_c is not None or store.orig_s is not None:
+        inside = rows.clamp(0, store.n_shapes - 1)            # a row outside the store has NaN points; its gather must stay in bounds
+        if store.orig_c is not None:
+            res['orig_c'] = store.orig_c.index_select(0, inside)
+        if store.orig_s is not None:
+            res['orig_s'] = store.orig_s.index_select(0, inside)
+    return res
+
+
+_ptr_or_null = lambda x: None if x is None else x.data_ptr()
+
+
+def sample_clouds(store, rows, cloud_size, return_eval_cloud=True, transform=None, state=None, explicit=None, out=None, permute=True):
+    """One batch: rows (B,) int32 shape indices on the store's device -> {'cloud': (B,3,cloud_size)[, 'eval_cloud'][, 'orig_c',
+    'orig_s']}, the keys and shapes of a collated reference batch.  Enqueued on the current stream; nothing waits for the device.
+
+    state: make_state(seed) (default: one the store keeps, seed 0).  explicit: {'words': (B,M) int32 bits of the uint32 face words,
+    's1', 's2': (B,M) float32, 'normals': (B,3,M) float32 when noise is on} replaces Philox (M = 2 * cloud_size with an eval cloud).
+    The scratch of a given (B, M) is allocated on the first call and kept on the store.  The returned tensors are fresh ones from
+    torch's allocator (which a graph capture records like any other); pass out={'cloud': ..., 'eval_cloud': ...} to write into
+    tensors of your own and allocate nothing at all.
+
+    A CloudStore goes to sample_stored_clouds with the same arguments (explicit and permute as described there); permute=False
+    means nothing for meshes and raises."""
+    if isinstance(store, CloudStore):
+        return sample_stored_clouds(store, rows, cloud_size, return_eval_cloud, transform, state, explicit, out, permute)
+    if not permute:
+        raise ValueError('permute=False asks for the stored order of a CloudStore; a MeshStore has none')
+    t, B, N, M, res, partials, state = _prepare_batch(store, rows, cloud_size, return_eval_cloud, transform, state, out)
+    dev = store.device
+    ex = _explicit_pointers(explicit, (('words', (B, M), torch.int32), ('s1', (B, M), torch.float32), ('s2', (B, M), torch.float32)) +
+                            ((('normals', (B, 3, M), torch.float32),) if t.noise else ()), dev)
+    ptr = _ptr_or_null
     a = _lib.CloudArgs(
         rows=rows.data_ptr(), vertices=store.vertices.data_ptr(), faces=store.faces.data_ptr(), thresholds=store.thresholds.data_ptr(),
         vertices_bounds=store.vertices_bounds.data_ptr(), faces_bounds=store.faces_bounds.data_ptr(),
@@ -235,13 +271,122 @@ def sample_clouds(store, rows, cloud_size, return_eval_cloud=True, transform=Non
         scale_div=t.scale_scale, noise_scale=t.noise_scale, stream=torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().gwtf_sample_clouds(ctypes.addressof(a)))
-    if store.orig_c is not None or store.orig_s is not None:
-        inside = rows.clamp(0, store.n_shapes - 1)            # a row outside the store has NaN points; its gather must stay in bounds
-        if store.orig_c is not None:
-            res['orig_c'] = store.orig_c.index_select(0, inside)
-        if store.orig_s is not None:
-            res['orig_s'] = store.orig_s.index_select(0, inside)
-    return res
+    return _with_original_frame(store, rows, res)
+
+
+class CloudStore:
+    """Point clouds that stay in device memory -- scans, a pre-sampled set, a frozen evaluation set -- packed as points (T,3)
+    float32 with bounds (S+1,) int64; cloud s is points[bounds[s]:bounds[s+1]].  It stands wherever a MeshStore stands
+    (sample_clouds, the loaders, the resident loops, evaluate_*): batches are drawn from the stored points, without replacement
+    while a batch row asks for no more points than its cloud holds (sample_stored_clouds)."""
+
+    def __init__(self):
+        raise TypeError('use CloudStore.from_arrays / CloudStore.from_mesh_store')
+
+    @classmethod
+    def from_arrays(cls, points, bounds=None, orig_c=None, orig_s=None, device='cuda'):
+        """points: (S, P, 3) equal-sized clouds, or packed (T, 3) with bounds (S+1,) ascending offsets into it."""
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+        if bounds is None:
+            if pts.ndim != 3 or pts.shape[2] != 3:
+                raise GwtfError('points must be (S, P, 3), or packed (T, 3) together with bounds')
+            b = np.arange(pts.shape[0] + 1, dtype=np.int64) * pts.shape[1]
+            pts = pts.reshape(-1, 3)
+        else:
+            if pts.ndim != 2 or pts.shape[1] != 3:
+                raise GwtfError('packed points must be (T, 3)')
+            b = np.asarray(bounds).astype(np.int64).reshape(-1)
+        cls._check_bounds(b, len(pts))
+        return cls._from_device(torch.from_numpy(pts).to(device), b, orig_c, orig_s)
+
+    @staticmethod
+    def _check_bounds(b, total):
+        n = len(b) - 1
+        if n < 1:
+            raise GwtfError('bounds must hold n_shapes + 1 entries, n_shapes >= 1')
+        if b[0] < 0 or b[-1] > total or np.any(np.diff(b) < 0):
+            raise GwtfError('bounds are not ascending offsets into points')
+        sizes = np.diff(b)
+        if np.any(sizes == 0):
+            raise GwtfError(f'cloud {int(np.flatnonzero(sizes == 0)[0])} has no points')
+        if np.any(sizes >= 2**31):
+            raise GwtfError(f'cloud {int(np.flatnonzero(sizes >= 2**31)[0])} has too many points')
+
+    @classmethod
+    def _from_device(cls, points, bounds_host, orig_c, orig_s):
+        self = object.__new__(cls)
+        n = len(bounds_host) - 1
+        self.n_shapes, self.bounds_host, self.device = n, bounds_host, points.device
+        self.points = points.contiguous()
+        self.bounds = torch.from_numpy(bounds_host).to(self.device)
+
+        def frame(a, shape):
+            if a is None:
+                return None
+            a = a.detach().to(torch.float32) if torch.is_tensor(a) else torch.from_numpy(np.asarray(a, np.float32))
+            return a.reshape(shape).contiguous().to(self.device)
+        self.orig_c, self.orig_s = frame(orig_c, (n, 3)), frame(orig_s, (n,))
+        self._work = {}
+        self._state = self._stored_order_state = None
+        return self
+
+    @classmethod
+    def from_mesh_store(cls, mesh_store, points_per_shape, seed=0, chunk=64):
+        """Freeze points_per_shape points of every mesh: sample_clouds(mesh_store, rows, points_per_shape, False, None, state) for
+        rows = chunk consecutive shapes at a time in store order, all calls on the one state make_state(seed)."""
+        P, S, dev = int(points_per_shape), len(mesh_store), mesh_store.device
+        if P < 1 or chunk < 1:
+            raise ValueError('points_per_shape and chunk must be positive')
+        state = make_state(seed, dev)
+        rows = torch.arange(S, dtype=torch.int32, device=dev)
+        parts = [sample_clouds(mesh_store, rows[i:i + chunk], P, False, None, state)['cloud'].transpose(1, 2) for i in range(0, S, chunk)]
+        return cls._from_device(torch.cat(parts).reshape(-1, 3), np.arange(S + 1, dtype=np.int64) * P, mesh_store.orig_c,
+                                mesh_store.orig_s)
+
+    def __len__(self):
+        return self.n_shapes
+
+    def clouds(self, rows=None, n_points=None):
+        """(len(rows), 3, n_points): the first n_points (default: as many as the smallest selected cloud holds) of each selected
+        cloud (default: all) in stored order -- a fixed set, e.g. the ref_clouds of evaluate_generation (which takes them
+        point-major: .transpose(1, 2)).  The states of the samplers do not move."""
+        idx = np.arange(self.n_shapes) if rows is None else np.asarray(rows.cpu() if torch.is_tensor(rows) else rows).astype(np.int64).reshape(-1)
+        if len(idx) < 1 or idx.min() < 0 or idx.max() >= self.n_shapes:
+            raise GwtfError(f'rows must name clouds in [0, {self.n_shapes})')
+        smallest = int(np.diff(self.bounds_host)[idx].min())
+        n = smallest if n_points is None else int(n_points)
+        if not 1 <= n <= smallest:
+            raise GwtfError(f'n_points must lie in [1, {smallest}], the size of the smallest selected cloud')
+        if self._stored_order_state is None and self.device.type == 'cuda':
+            self._stored_order_state = make_state(0, self.device)
+        out = []
+        for i in range(0, len(idx), 65535):
+            r = torch.from_numpy(idx[i:i + 65535].astype(np.int32)).to(self.device)
+            out.append(sample_stored_clouds(self, r, n, False, None, self._stored_order_state, permute=False)['cloud'])
+        return out[0] if len(out) == 1 else torch.cat(out)
+
+
+def sample_stored_clouds(store, rows, cloud_size, return_eval_cloud=True, transform=None, state=None, explicit=None, out=None,
+                         permute=True):
+    """sample_clouds for a CloudStore: the same arguments, checks, out= contract and returned keys.  Point j of a row is the stored
+    point at the index the keyed bijection of include/gwtf.h (GwtfStoredCloudArgs) gives: without replacement while M = (2 *)
+    cloud_size stays at or below the cloud's size -- cloud and eval_cloud are then disjoint -- and wrapping into a fresh permutation
+    past it.  permute=False: the stored order.  explicit: {'index': (B,M) int32 point indices, 'normals': (B,3,M) float32 when noise
+    is on}; an index outside its cloud gives a NaN point."""
+    t, B, N, M, res, partials, state = _prepare_batch(store, rows, cloud_size, return_eval_cloud, transform, state, out)
+    dev = store.device
+    ex = _explicit_pointers(explicit, (('index', (B, M), torch.int32),) + ((('normals', (B, 3, M), torch.float32),) if t.noise else ()), dev)
+    ptr = _ptr_or_null
+    a = _lib.StoredCloudArgs(
+        rows=rows.data_ptr(), points=store.points.data_ptr(), bounds=store.bounds.data_ptr(), orig_c=ptr(store.orig_c),
+        orig_s=ptr(store.orig_s), cloud=_lib._ptr(res['cloud'], 'cloud'), eval_cloud=_lib._ptr(res.get('eval_cloud'), 'eval_cloud'),
+        partials=ptr(partials), state=state.data_ptr(), index=ex.get('index'), normals=ex.get('normals'), B=B, M=M,
+        n_shapes=store.n_shapes, rescale=t.rescale2orig, recenter=t.recenter2orig, translate=t.translate, scale=t.scale, noise=t.noise,
+        center=t.center, permute=bool(permute), tune=_lib.tune_word(), shift=(ctypes.c_float * 3)(*t.translate_shift),
+        scale_div=t.scale_scale, noise_scale=t.noise_scale, stream=torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().gwtf_sample_stored_clouds(ctypes.addressof(a)))
+    return _with_original_frame(store, rows, res)
 
 
 _IDENTITY = CloudTransform()
@@ -268,10 +413,12 @@ class DeviceCloudLoader:
     """Stands where DataLoader(ShapeNetCoreDataset(...), batch_size, shuffle=True, drop_last=True) stood (train_ae.py:85-116): an
     iterable of device batches.  The epoch's order is a host permutation from (seed, epoch) -- torch.randperm under a generator
     seeded seed + epoch, and for world_size > 1 the padding and stride of torch.utils.data.DistributedSampler, whose indices a rank
-    therefore reproduces; the points come from the device sampler, whose state lives on the device and advances by itself."""
+    therefore reproduces; the points come from the device sampler, whose state lives on the device and advances by itself.
+    store: a MeshStore or a CloudStore.  permute=False (CloudStore only) reads every cloud in its stored order, so the loader
+    yields the same clouds every epoch -- a frozen validation set."""
 
     def __init__(self, store, batch_size, cloud_size, transform=None, shuffle=True, drop_last=True, seed=0, rank=0, world_size=1,
-                 return_eval_cloud=True):
+                 return_eval_cloud=True, permute=True):
         if not 0 <= rank < world_size:
             raise ValueError('rank must lie in [0, world_size)')
         if batch_size < 1:
@@ -279,6 +426,9 @@ class DeviceCloudLoader:
         self.store, self.batch_size, self.cloud_size, self.transform = store, int(batch_size), int(cloud_size), transform
         self.shuffle, self.drop_last, self.seed, self.rank, self.world_size = bool(shuffle), bool(drop_last), int(seed), rank, world_size
         self.return_eval_cloud = bool(return_eval_cloud)
+        self.permute = bool(permute)                                  # False: a CloudStore's points in stored order, every epoch
+        if not self.permute and not isinstance(store, CloudStore):
+            raise ValueError('permute=False asks for the stored order of a CloudStore; a MeshStore has none')
         self.epoch = 0
         self.num_samples = -(-len(store) // world_size)               # DistributedSampler, drop_last=False: ceil
         self._state = None
@@ -301,4 +451,4 @@ class DeviceCloudLoader:
         rows = torch.from_numpy(self.index_plan().astype(np.int32)).to(dev)
         for b in range(len(self)):
             yield sample_clouds(self.store, rows[b * self.batch_size:(b + 1) * self.batch_size], self.cloud_size,
-                                self.return_eval_cloud, self.transform, self._state)
+                                self.return_eval_cloud, self.transform, self._state, permute=self.permute)

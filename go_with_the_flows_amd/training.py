@@ -296,7 +296,8 @@ class ResidentTrainLoop:
             sample_clouds(loader.mesh_store, self.mesh_rows, loader.cloud_size, True, loader.cloud_transform, loader._state, out=out)
             transform_images(loader.image_store, self.rows, loader.image_transform, loader._image_state, out=self.i_static)
         else:
-            sample_clouds(loader.store, self.rows, loader.cloud_size, True, loader.transform, loader._state, out=out)
+            sample_clouds(loader.store, self.rows, loader.cloud_size, True, loader.transform, loader._state, out=out,
+                          permute=getattr(loader, 'permute', True))
         self.terms = GraphedTrainStep._fwd_bwd(self)
         if any(t.dtype != torch.float32 or not t.is_cuda for t in self.terms):
             raise _lib.GwtfError('the criterion must return four float32 device scalars')
@@ -469,7 +470,7 @@ class ResidentEvalLoop:
         with torch.cuda.device(dev):
             _lib.check(L.gwtf_loop_begin(ctypes.addressof(a)))
         sample_clouds(loader.store, self.rows, loader.cloud_size, True, loader.transform, loader._state,
-                      out={'cloud': self.g_static, 'eval_cloud': self.p_static})
+                      out={'cloud': self.g_static, 'eval_cloud': self.p_static}, permute=getattr(loader, 'permute', True))
         enc, dec = self.model.forward_fused(self.g_static, self.p_static, warmup)
         terms = tuple(t.detach() for t in self.criterion.fused(enc, dec))
         if len(terms) != 4 or any(t.dtype != torch.float32 or not t.is_cuda for t in terms):

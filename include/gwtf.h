@@ -708,6 +708,55 @@ int gwtf_cloud_partials(int M);
  * <= 0 where enabled, explicit draws given in part (reference cloud_sampling.py:4-32). */
 int gwtf_sample_clouds(const GwtfCloudArgs* args);
 
+/* Batches drawn from STORED clouds (csrc/gwtf_clouds.hip, cloud_gather_kernel; added without a version change: no existing entry or
+ * record moved).  A store holds n_shapes clouds packed as points [T][3] with bounds [n_shapes + 1]; cloud s has
+ * P = bounds[s + 1] - bounds[s] points, 1 <= P < 2^31.  Draw j in [0, M) of batch row r, shape s = rows[r], takes the stored point
+ * at an INDEX in [0, P):
+ *   Round and slot: q = j / P, t = j % P.  Within a round distinct j give distinct points -- the draw is without replacement while
+ *   M <= P, so cloud and eval_cloud are disjoint; past P it wraps into a new permutation, and every point is used floor(M / P) or
+ *   ceil(M / P) times.
+ *   Index: a keyed bijection on [0, P).  b = max(1, ceil(log2 P)), h = (b + 1) / 2, domain 2^(2h) (P <= domain < 4P for P > 1).  Six
+ *   round keys: K0..K3 the four words of the Philox4x32-10 block with key (seed lo, seed hi) and counter
+ *   (2q, r, call lo, call hi | 2 << 28), K4 K5 the first two words of the block with counter (2q + 1, r, call lo, call hi | 2 << 28)
+ *   -- stream 2; streams 0 and 1 keep the meaning they have in gwtf_sample_clouds.  Start x = t and repeat until x < P:
+ *   L = x >> h, R = x & (2^h - 1); for i = 0..5: (L, R) = (R, L ^ (fmix32(R ^ K_i) >> (32 - h))); x = (L << h) | R.  fmix32 is
+ *   murmur3's finaliser: x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16.  The walk follows the cycle of
+ *   t in a permutation of the domain, so it returns to [0, P); it is cut at 1024 steps all the same, and then yields a NaN point.
+ *   permute = 0: index = t, the stored order (fixed sets).
+ *   With `index` non-NULL the indices are read instead (tests, fixtures); one outside [0, P) yields a NaN point and reads nothing.
+ * Everything behind the index is gwtf_sample_clouds': even j to cloud[r][:][j/2] and odd j to eval_cloud with an eval cloud, the six
+ * transformations in the same order and the same float32 statements, noise from stream 1 with counter (j, r, ...) or from
+ * `normals` with explicit indices, per-tile sums of 256 points in the same fixed tree, the same finishing launch (centring, call + 1).
+ * A NaN point adds nothing to its tile's sums.  A row index outside [0, n_shapes) yields NaN points and reads nothing.  Results do
+ * not depend on the tuning word. */
+typedef struct GwtfStoredCloudArgs {
+  const int* rows;                   /* [B] shape indices, repeats allowed */
+  const float* points;               /* [T][3] all shapes' points */
+  const long long* bounds;           /* [n_shapes + 1] */
+  const float* orig_c;               /* [n_shapes][3], read when recenter */
+  const float* orig_s;               /* [n_shapes], read when rescale */
+  float* cloud;                      /* [B][3][N], N = M / 2 with an eval cloud, else M */
+  float* eval_cloud;                 /* [B][3][N] or NULL */
+  float* partials;                   /* [B][gwtf_cloud_partials(M)][6] scratch, written and read when center */
+  unsigned long long* state;         /* {seed, call} */
+  const int* index;                  /* explicit draws: [B][M] point indices, or NULL (the rule above) */
+  const float* normals;              /* [B][3][M] standard normals, read when noise and index */
+  int B, M, n_shapes;
+  int rescale, recenter, translate, scale, noise, center;   /* as in GwtfCloudArgs */
+  int permute;                       /* 0: the stored order */
+  int tune;                          /* as in GwtfCloudArgs */
+  float shift[3];
+  float scale_div;
+  float noise_scale;
+  void* stream;
+} GwtfStoredCloudArgs;
+/* GWTF_E_BADARG without a launch: a NULL record or required pointer, B outside 1..65535, M < 1, odd M with an eval cloud, scale_div /
+ * noise_scale <= 0 where enabled, normals without index, index without normals when noise. */
+int gwtf_sample_stored_clouds(const GwtfStoredCloudArgs* args);
+/* The index rule above on the host: the image of t under the permutation of [0, P) keyed by keys6[0..5]; 0xffffffff for a NULL
+ * keys6, t >= P, P outside [1, 2^31) and at the 1024-step cap. */
+unsigned gwtf_perm_index(const unsigned* keys6, unsigned t, unsigned P);
+
 /* Device-resident generation (ABI 10 gained these entry points; no existing record or signature changed): every point of S generated
  * clouds draws its mixture component and its base sample on the device and is laid out so that ONE stack launch sends it through its
  * own component -- the sampling branch of Flow_Mixture_Model.decode (lib/networks/flow_mixture.py:146-177: np.random.choice over the
