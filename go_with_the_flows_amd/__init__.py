@@ -13,7 +13,7 @@ from .resnet import ResNet, BasicBlock, resnet18
 from .clouds import MeshStore, CloudStore, CloudTransform, DeviceCloudLoader, sample_clouds, sample_stored_clouds, make_state
 from .images import ImageStore, ImageTransform, DeviceSVRLoader, transform_images
 from .metrics import EvalFrame, clouds_to_eval_frame, chamfer_paired, paired_metrics
-from .evaluation import evaluate_generation, evaluate_autoencoding, evaluate_reconstruction
+from .evaluation import evaluate_generation, evaluate_autoencoding, evaluate_reconstruction, interpolate_clouds, upsample_clouds
 from ._lib import GwtfError
 
 __all__ = ['SharedDot', 'Swish', 'CondRealNVPFlow3D', 'CondRealNVPFlow3DTriple', 'LocalCondRNVPDecoder',
@@ -23,4 +23,5 @@ __all__ = ['SharedDot', 'Swish', 'CondRealNVPFlow3D', 'CondRealNVPFlow3DTriple',
            'Flow_Mixture_Model', 'Flow_Mixture_SVR_Model', 'Flow_Mixture_Loss', 'FlowMixtureNLL', 'ResNet', 'BasicBlock',
            'resnet18', 'MeshStore', 'CloudStore', 'CloudTransform', 'DeviceCloudLoader', 'sample_clouds', 'sample_stored_clouds', 'make_state',
            'ImageStore', 'ImageTransform', 'DeviceSVRLoader', 'transform_images', 'EvalFrame', 'clouds_to_eval_frame',
-           'chamfer_paired', 'paired_metrics', 'evaluate_generation', 'evaluate_autoencoding', 'evaluate_reconstruction']
+           'chamfer_paired', 'paired_metrics', 'evaluate_generation', 'evaluate_autoencoding', 'evaluate_reconstruction',
+           'interpolate_clouds', 'upsample_clouds']

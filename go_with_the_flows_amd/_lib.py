@@ -113,6 +113,8 @@ _SIGNATURES = {
     'gwtf_route_tiles': (ctypes.c_int, [ctypes.c_int] * 3),
     'gwtf_mixture_route': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_stack_forward_routed': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_mixture_route_sweep': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_film_forward_k': (ctypes.c_int, [_c_fp, _c_fp, _c_fp] + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_longlong, _c_fp]),
     'gwtf_transform_images': (ctypes.c_int, [ctypes.c_void_p]),
     'gwtf_norm2d_partials': (ctypes.c_int, [ctypes.c_int] * 4),
     'gwtf_norm2d_forward': (ctypes.c_int, [ctypes.c_void_p]),
@@ -228,6 +230,13 @@ class RouteArgs(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_void_p) for n in ('logits', 'mu0', 'lv0', 'state', 'words', 'labels_in', 'normals', 'z0_in', 'thresholds',
                                                 'tile_comp', 'perm', 'zp', 'labels')] +
                 [(n, ctypes.c_int) for n in ('S', 'n', 'K', 'P', 'mu0_stride', 'lv0_stride')] + [('stream', ctypes.c_void_p)])
+
+
+class RouteSweepArgs(ctypes.Structure):
+    """GwtfRouteSweepArgs of include/gwtf.h (GwtfRouteArgs for R rows that share draws in groups, one base per component): same field
+    order."""
+    _fields_ = (RouteArgs._fields_[:-1] + [(n, ctypes.c_int) for n in ('group', 'mu0_stride_k', 'lv0_stride_k')] +
+                [('stream', ctypes.c_void_p)])
 
 
 class RoutedStackArgs(ctypes.Structure):
@@ -418,6 +427,20 @@ def film_forward(g, packed_film, C, f, eps):
     with torch.cuda.device(g.device):
         check(L.gwtf_film_forward(_ptr(g, 'g'), _ptr(packed_film, 'packed_film'), _ptr(out, 'film_out'), B, G, C, f, float(eps),
                                   _stream(g)))
+    return out
+
+
+def film_forward_k(gk, packed_film, Cper, f, eps):
+    """film_forward with a latent table per component: gk (K, B, G) -> the (B, K*Cper, 6FP+4) record, component k's couplings
+    conditioned on gk[k] (gwtf_film_forward_k; eval-mode BatchNorm)."""
+    L = lib()
+    if gk.dim() != 3:
+        raise GwtfError(f'gk must be (K, B, G), got {tuple(gk.shape)}')
+    K, B, G = gk.shape
+    out = torch.empty(B, K * Cper, L.gwtf_film_out_floats(f), device=gk.device, dtype=torch.float32)
+    with torch.cuda.device(gk.device):
+        check(L.gwtf_film_forward_k(_ptr(gk, 'gk'), _ptr(packed_film, 'packed_film'), _ptr(out, 'film_out'), B, G, K, Cper, f,
+                                    float(eps), B * G, _stream(gk)))
     return out
 
 
@@ -634,6 +657,39 @@ def mixture_route(work, logits=None, mu0=None, lv0=None, state=None, words=None,
                   stream=torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
         check(lib().gwtf_mixture_route(ctypes.addressof(a)))
+    return work
+
+
+def mixture_route_sweep(work, group=1, logits=None, mu0=None, lv0=None, state=None, words=None, labels_in=None, normals=None,
+                        z0_in=None):
+    """gwtf_mixture_route_sweep on the current stream into the buffers of `work` (route_scratch for R rows): row r takes the draws of
+    shape r // group.  logits (R, K) float32; mu0 / lv0 (R, 3) or (1, 3) -- one base for all components -- or (K, R, 3) / (K, 1, 3), a
+    base per component; the explicit draws are those of mixture_route with S = R // group rows."""
+    R, n = work['labels'].shape
+    K, dev = work['thresholds'].shape[1], work['labels'].device
+    group = int(group)
+    if group < 1 or R % group:
+        raise GwtfError(f'group must be a positive divisor of the {R} rows, got {group}')
+    S = R // group
+    if state is not None and (state.dtype != torch.int64 or state.numel() != 2 or state.device != dev):
+        raise GwtfError('state must come from make_state(seed, device) on the device of the call')
+    f32, i32 = torch.float32, torch.int32
+    base = []
+    for t, name in ((mu0, 'mu0'), (lv0, 'lv0')):
+        if t is not None and (t.dim() not in (2, 3) or t.shape[-2] not in (1, R) or t.shape[-1] != 3 or (t.dim() == 3 and t.shape[0] != K)):
+            raise GwtfError(f'{name} must be (R, 3), (1, 3), (K, R, 3) or (K, 1, 3), got {tuple(t.shape)}')
+        rows = 0 if t is None else t.shape[-2]
+        base.append((_ptr(t, name), 0 if rows <= 1 else 3, 0 if t is None or t.dim() == 2 else 3 * rows))
+    a = RouteSweepArgs(logits=_explicit(logits, 'logits', (R, K), f32, dev), mu0=base[0][0], lv0=base[1][0],
+                       state=None if state is None else state.data_ptr(), words=_explicit(words, 'words', (S, n), i32, dev),
+                       labels_in=_explicit(labels_in, 'labels_in', (S, n), i32, dev),
+                       normals=_explicit(normals, 'normals', (S, 3, n), f32, dev), z0_in=_explicit(z0_in, 'z0_in', (S, 3, n), f32, dev),
+                       thresholds=work['thresholds'].data_ptr(), tile_comp=work['tile_comp'].data_ptr(), perm=work['perm'].data_ptr(),
+                       zp=work['zp'].data_ptr(), labels=work['labels'].data_ptr(), S=R, n=n, K=K, P=work['P'],
+                       mu0_stride=base[0][1], lv0_stride=base[1][1], group=group, mu0_stride_k=base[0][2], lv0_stride_k=base[1][2],
+                       stream=torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        check(lib().gwtf_mixture_route_sweep(ctypes.addressof(a)))
     return work
 
 

@@ -39,9 +39,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // kGCH = latent columns per register-resident chunk: 128 keeps a G = 128 head in ONE load round (shortest chain; 150 VGPRs,
 // 3 workgroups per CU), 64 takes two rounds but 4-5 workgroups fit a CU -- chosen when the grid exceeds one round of the
 // former (the K x C couplings of a mixture: 19.8 -> 17.1 us on the airplane grid of 1056 workgroups).
-template <int MB, int kGCH>
+// PerK: empty (gwtf_film_forward; the kernel as it always was, instruction for instruction), or (int Cper, long long g_stride_k) of
+// gwtf_film_forward_k: coupling c reads the latent rows of ITS component -- K tables of B rows, g_stride_k floats apart, the couplings
+// laid out component by component, Cper per component.
+__device__ __forceinline__ size_t film_table_offset(int c, int Cper, long long g_stride_k) { return (size_t)(c / Cper) * (size_t)g_stride_k; }
+
+template <int MB, int kGCH, class... PerK>
 __global__ __launch_bounds__(MB > 4 ? 512 : 256) void film_eval_kernel(const float* __restrict__ g, const float* __restrict__ pf,
-                                                        float* __restrict__ out, int B, int G, int C, int f, float eps) {
+                                                        float* __restrict__ out, int B, int G, int C, int f, float eps, PerK... per_k) {
   constexpr int FP = 16 * MB;
   __shared__ __align__(16) float hb[2][16][FP + 4];   // [head][shape][feature]
   const int c = blockIdx.x, br = blockIdx.y, b0 = blockIdx.z * kBTe;
@@ -54,7 +59,9 @@ __global__ __launch_bounds__(MB > 4 ? 512 : 256) void film_eval_kernel(const flo
   const bool own = wave < MB;                        // this wave's feature block exists
   const int ft = 16 * wave + i16;                    // output feature owned by this lane (both heads)
   const int brow = b0 + i16;                         // shape whose latent row this lane feeds to the A operand
-  const float* grow = g + (size_t)(brow < B ? brow : B - 1) * G;
+  const float* table = g;
+  if constexpr (sizeof...(PerK) != 0) table += film_table_offset(c, per_k...);
+  const float* grow = table + (size_t)(brow < B ? brow : B - 1) * G;
   const float* l0 = w + P.l0t(0) + 4 * ft;           // L0Q[col/4][ft][col%4] (gwtf_layout.h)
   const float* l1 = w + P.l0t(1) + 4 * ft;
   const bool gvec = (G & 3) == 0;                    // latent rows are 16-byte aligned and whole quads
@@ -176,5 +183,31 @@ extern "C" int gwtf_film_forward(const float* g, const float* packed_film, float
     default: GWTF_FILM_EVAL(8); break;
   }
 #undef GWTF_FILM_EVAL
+  return (int)hipGetLastError();
+}
+
+extern "C" int gwtf_film_forward_k(const float* g, const float* packed_film, float* film_out, int B, int G, int K, int Cper, int f, float eps,
+                                   long long g_stride_k, void* stream) {
+  if (B <= 0 || G <= 0 || K <= 0 || Cper <= 0 || (long long)K * Cper > 0x7fffffffLL || g_stride_k < 0 || f <= 0 || f > GWTF_MAX_FP || !g ||
+      !packed_film || !film_out)
+    return GWTF_E_BADARG;
+  const int FP = gwtf_padded_width(f), C = K * Cper;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(C, 2, (B + kBTe - 1) / kBTe);
+  const bool many = (long)grid.x * grid.y * grid.z > 768;   // the choice of gwtf_film_forward at the same grid
+#define GWTF_FILM_EVAL_K(MB_)                                                                                                \
+  if (many) hipLaunchKernelGGL((film_eval_kernel<MB_, 64, int, long long>), grid, dim3(MB_ > 4 ? 512 : 256), 0, st, g, packed_film, film_out, B, G, C, f, eps, Cper, g_stride_k); \
+  else hipLaunchKernelGGL((film_eval_kernel<MB_, 128, int, long long>), grid, dim3(MB_ > 4 ? 512 : 256), 0, st, g, packed_film, film_out, B, G, C, f, eps, Cper, g_stride_k)
+  switch (FP / 16) {
+    case 1: GWTF_FILM_EVAL_K(1); break;
+    case 2: GWTF_FILM_EVAL_K(2); break;
+    case 3: GWTF_FILM_EVAL_K(3); break;
+    case 4: GWTF_FILM_EVAL_K(4); break;
+    case 5: GWTF_FILM_EVAL_K(5); break;
+    case 6: GWTF_FILM_EVAL_K(6); break;
+    case 7: GWTF_FILM_EVAL_K(7); break;
+    default: GWTF_FILM_EVAL_K(8); break;
+  }
+#undef GWTF_FILM_EVAL_K
   return (int)hipGetLastError();
 }

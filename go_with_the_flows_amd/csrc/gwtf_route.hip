@@ -10,6 +10,8 @@
 // and the padding behind every component's last point is filled (perm -1, zp 0).  Thread i handles point chunk * 256 + i in both
 // passes and reads back only labels it wrote itself.  Counts are integer LDS atomics, nothing is added in global memory: the
 // outputs are a function of the labels alone.  A one-thread finishing launch stores call + 1, as the cloud sampler's does.
+// The same body serves latent sweeps (gwtf_mixture_route_sweep): rows that share the draws of one shape in groups, each with its own
+// logits and, per component, its own base Gaussian.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/gwtf.h"
@@ -24,15 +26,23 @@ constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kMaxK = GWTF_MAX_COMPONENTS;
 constexpr uint32_t kStreamLabel = 2u, kStreamNormal = 3u;      // Philox streams (the cloud sampler uses 0 and 1)
 
-__global__ __launch_bounds__(kThreads) void route_kernel(GwtfRouteArgs a, int tiles) {
+// SWEEP (gwtf_mixture_route_sweep, Args = GwtfRouteSweepArgs): row r of R = a.S rows draws what shape r / group draws -- the Philox shape
+// coordinate and the row of every explicit array are r / group -- while its logits, its base Gaussians and its outputs are its own; the
+// base of a point is that of ITS component, K tables a.mu0_stride_k floats apart, read from LDS by the label in pass 2.
+// route_kernel<false, GwtfRouteArgs> is the routing launch as it always was, instruction for instruction.
+template <bool SWEEP, class Args>
+__global__ __launch_bounds__(kThreads) void route_kernel(Args a, int tiles) {
   __shared__ double cdf[kMaxK];
   __shared__ uint32_t thr[kMaxK];
   __shared__ int count[kMaxK], next_slot[kMaxK], tile_start[kMaxK + 1], wave_count[kWaves][kMaxK];
+  __shared__ float mu_k[SWEEP ? kMaxK : 1][3], sd_k[SWEEP ? kMaxK : 1][3];
   const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int sdraw = s;                                               // whose draws this row takes
+  if constexpr (SWEEP) sdraw = s / a.group;
   const int n = a.n, K = a.K, P = a.P;
   const size_t NP = (size_t)tiles * P;
-  const int* words = a.words ? a.words + (size_t)s * n : nullptr;
-  const int* labels_in = a.labels_in ? a.labels_in + (size_t)s * n : nullptr;
+  const int* words = a.words ? a.words + (size_t)sdraw * n : nullptr;
+  const int* labels_in = a.labels_in ? a.labels_in + (size_t)sdraw * n : nullptr;
   int* labels = a.labels + (size_t)s * n;
   int* perm = a.perm + (size_t)s * NP;
   float* zp = a.zp + (size_t)s * 3 * NP;
@@ -56,6 +66,15 @@ __global__ __launch_bounds__(kThreads) void route_kernel(GwtfRouteArgs a, int ti
 #pragma unroll
     for (int w = 0; w < kWaves; ++w) wave_count[w][k] = 0;
   }
+  if constexpr (SWEEP) {
+    if (!a.z0_in) {
+      for (int j = tid; j < 3 * K; j += kThreads) {            // read in pass 2, behind the barriers below
+        const int k = j / 3, d = j - 3 * k;
+        mu_k[k][d] = a.mu0[(size_t)s * a.mu0_stride + (size_t)k * a.mu0_stride_k + d];
+        sd_k[k][d] = expf(0.5f * a.lv0[(size_t)s * a.lv0_stride + (size_t)k * a.lv0_stride_k + d]);
+      }
+    }
+  }
   __syncthreads();
   if (!labels_in && a.thresholds && tid < K) a.thresholds[(size_t)s * K + tid] = (int)thr[tid];
 
@@ -74,7 +93,7 @@ __global__ __launch_bounds__(kThreads) void route_kernel(GwtfRouteArgs a, int ti
       if (labels_in) {
         lab = min(max(labels_in[i], 0), K - 1);                // every position computed below stays inside the shape's slots
       } else {
-        const uint32_t w = words ? (uint32_t)words[i] : philox4x32_10((uint32_t)i, (uint32_t)s, c2, c3 | (kStreamLabel << 28), k0, k1).x;
+        const uint32_t w = words ? (uint32_t)words[i] : philox4x32_10((uint32_t)i, (uint32_t)sdraw, c2, c3 | (kStreamLabel << 28), k0, k1).x;
         lab = 0;
         for (int k = 0; k + 1 < K; ++k) lab += thr[k] <= w ? 1 : 0;
       }
@@ -107,7 +126,7 @@ __global__ __launch_bounds__(kThreads) void route_kernel(GwtfRouteArgs a, int ti
   }
 
   float mu[3] = {0.f, 0.f, 0.f}, sd[3] = {1.f, 1.f, 1.f};
-  if (!a.z0_in) {
+  if (!SWEEP && !a.z0_in) {
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
       mu[d] = a.mu0[(size_t)s * a.mu0_stride + d];
@@ -147,17 +166,21 @@ __global__ __launch_bounds__(kThreads) void route_kernel(GwtfRouteArgs a, int ti
     if (live && slot >= 0 && (size_t)slot < NP) {
       float z[3];
       if (a.z0_in) {
-        const float* src = a.z0_in + (size_t)s * 3 * n + i;
+        const float* src = a.z0_in + (size_t)sdraw * 3 * n + i;
         z[0] = src[0]; z[1] = src[n]; z[2] = src[2 * (size_t)n];
       } else {
         float e[4];
         if (a.normals) {
-          const float* src = a.normals + (size_t)s * 3 * n + i;
+          const float* src = a.normals + (size_t)sdraw * 3 * n + i;
           e[0] = src[0]; e[1] = src[n]; e[2] = src[2 * (size_t)n];
         } else {
-          const Philox4 d = philox4x32_10((uint32_t)i, (uint32_t)s, c2, c3 | (kStreamNormal << 28), k0, k1);
+          const Philox4 d = philox4x32_10((uint32_t)i, (uint32_t)sdraw, c2, c3 | (kStreamNormal << 28), k0, k1);
           box_muller(d.x, d.y, e[0], e[1]);
           box_muller(d.z, d.w, e[2], e[3]);
+        }
+        if constexpr (SWEEP) {
+#pragma unroll
+          for (int d = 0; d < 3; ++d) { mu[d] = mu_k[lab][d]; sd[d] = sd_k[lab][d]; }
         }
 #pragma unroll
         for (int d = 0; d < 3; ++d) z[d] = e[d] * sd[d] + mu[d];  // reparameterize's order (the library is built -ffp-contract=off)
@@ -189,17 +212,34 @@ extern "C" int gwtf_route_tiles(int n, int K, int P) {
   return (int)(((long long)n + (long long)K * (P - 1)) / P);
 }
 
-extern "C" int gwtf_mixture_route(const GwtfRouteArgs* pa) {
-  if (!pa) return GWTF_E_BADARG;
-  const GwtfRouteArgs& a = *pa;
-  if (a.S < 1 || a.n < 1 || a.K < 1 || a.K > kMaxK || (a.P != 64 && a.P != 128 && a.P != 256)) return GWTF_E_BADARG;
-  if (!a.tile_comp || !a.perm || !a.zp || !a.labels) return GWTF_E_BADARG;
-  if (!a.labels_in && (!a.logits || (!a.words && !a.state))) return GWTF_E_BADARG;
-  if (!a.z0_in && (!a.mu0 || !a.lv0 || a.mu0_stride < 0 || a.lv0_stride < 0 || (!a.normals && !a.state))) return GWTF_E_BADARG;
+// what both entry points refuse
+template <class Args>
+static bool route_args_ok(const Args& a) {
+  if (a.S < 1 || a.n < 1 || a.K < 1 || a.K > kMaxK || (a.P != 64 && a.P != 128 && a.P != 256)) return false;
+  if (!a.tile_comp || !a.perm || !a.zp || !a.labels) return false;
+  if (!a.labels_in && (!a.logits || (!a.words && !a.state))) return false;
+  if (!a.z0_in && (!a.mu0 || !a.lv0 || a.mu0_stride < 0 || a.lv0_stride < 0 || (!a.normals && !a.state))) return false;
   const int tiles = gwtf_route_tiles(a.n, a.K, a.P);
-  if (tiles < 1 || (long long)a.S * tiles > 0x7fffffffLL / a.P) return GWTF_E_BADARG;
+  return tiles >= 1 && (long long)a.S * tiles <= 0x7fffffffLL / a.P;
+}
+
+extern "C" int gwtf_mixture_route(const GwtfRouteArgs* pa) {
+  if (!pa || !route_args_ok(*pa)) return GWTF_E_BADARG;
+  const GwtfRouteArgs& a = *pa;
+  const int tiles = gwtf_route_tiles(a.n, a.K, a.P);
   hipStream_t st = (hipStream_t)a.stream;
-  hipLaunchKernelGGL(route_kernel, dim3((unsigned)a.S), dim3(kThreads), 0, st, a, tiles);
+  hipLaunchKernelGGL((route_kernel<false, GwtfRouteArgs>), dim3((unsigned)a.S), dim3(kThreads), 0, st, a, tiles);
+  if (a.state) hipLaunchKernelGGL(route_finish_kernel, dim3(1), dim3(1), 0, st, a.state);
+  return (int)hipGetLastError();
+}
+
+extern "C" int gwtf_mixture_route_sweep(const GwtfRouteSweepArgs* pa) {
+  if (!pa || !route_args_ok(*pa)) return GWTF_E_BADARG;
+  const GwtfRouteSweepArgs& a = *pa;
+  if (a.group < 1 || a.S % a.group != 0 || a.mu0_stride_k < 0 || a.lv0_stride_k < 0) return GWTF_E_BADARG;
+  const int tiles = gwtf_route_tiles(a.n, a.K, a.P);
+  hipStream_t st = (hipStream_t)a.stream;
+  hipLaunchKernelGGL((route_kernel<true, GwtfRouteSweepArgs>), dim3((unsigned)a.S), dim3(kThreads), 0, st, a, tiles);
   if (a.state) hipLaunchKernelGGL(route_finish_kernel, dim3(1), dim3(1), 0, st, a.state);
   return (int)hipGetLastError();
 }

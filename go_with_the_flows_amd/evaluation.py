@@ -393,6 +393,64 @@ def evaluate_reconstruction(model, batches, n_points, f1_threshold_lst=(0.0001,)
                             f1_threshold_lst, cd, emd, f1, frame)
 
 
+def _posterior_means(model, clouds):
+    """encode(clouds)['g_posterior_mus'] in any model.mode: the cloud encoder and the posterior head, nothing else."""
+    return model.g_posterior(model._pooled_features(clouds))[0]
+
+
+@torch.no_grad()
+def interpolate_clouds(model, batches, n_points, n_batches=3, weights=None, flow_idx=None, state=None, generator=None):
+    """The reference's `interpolate` (evaluating.py:269-382, the `--interpolation` / `--interpolate_one_flow --flow_idx` branches of
+    evaluate_ae.py, kept inside a string literal there) on the device.  ``batches``: device dicts with 'cloud' and 'eval_cloud'
+    (DeviceCloudLoader); the first ``n_batches`` are used.  Per batch 'cloud' is paired with a permutation of 'eval_cloud' --
+    torch.randperm on the device with ``generator`` where the reference shuffles with np.random -- both codes are the posterior
+    means, and Flow_Mixture_Model.interpolate_many (``weights``, default np.arange(1, 10) / 10; ``flow_idx``; ``state``) decodes the T
+    steps of every pair with shared draws.  Nothing is read back.
+    -> {'clouds1' (N, 3, M), 'clouds2' (N, 3, M), 'interpolations' (N, 3, n_points, T) float32, 'labels' (N, n_points, T) uint8},
+    device tensors with the names and layouts of the reference's h5 datasets; writing the file is the caller's."""
+    if n_batches < 1:
+        raise ValueError('n_batches must be positive')
+    parts = {'clouds1': [], 'clouds2': [], 'interpolations': [], 'labels': []}
+    for i, batch in enumerate(batches):
+        if i == n_batches:
+            break
+        batch = _device_batch(batch, False)
+        clouds, ref = batch['cloud'], batch['eval_cloud']
+        ref = ref[torch.randperm(ref.shape[0], device=ref.device, generator=generator)].contiguous()
+        x, labels = model.interpolate_many(_posterior_means(model, clouds), _posterior_means(model, ref), n_points, weights=weights,
+                                           flow_idx=flow_idx, return_labels=True, state=state)
+        parts['clouds1'].append(clouds)
+        parts['clouds2'].append(ref)
+        parts['interpolations'].append(x.permute(0, 2, 3, 1))               # (S, T, 3, n) -> (S, 3, n, T)
+        parts['labels'].append(labels.permute(0, 2, 1).to(torch.uint8))     # (S, T, n) -> (S, n, T)
+    if not parts['clouds1']:
+        raise GwtfError('no batches: the iterable is empty')
+    return {k: torch.cat(v).contiguous() for k, v in parts.items()}
+
+
+@torch.no_grad()
+def upsample_clouds(model, batches, sparse_size, n_points, n_batches=10, state=None):
+    """The reference's `sample` (evaluating.py:384-457, the `--sampling` branch of evaluate_ae.py, kept inside a string literal
+    there) on the device: the first ``sparse_size`` points of every 'cloud' of the first ``n_batches`` batches are encoded and
+    Flow_Mixture_Model.upsample_many decodes ``n_points`` points from the posterior means, with a component label per point.
+    -> {'clouds_sparse' (N, 3, sparse_size), 'clouds_dense' (N, 3, n_points) float32, 'labels' (N, n_points) uint8}, device tensors
+    with the names and layouts of the reference's h5 datasets."""
+    if n_batches < 1 or sparse_size < 1:
+        raise ValueError('n_batches and sparse_size must be positive')
+    parts = {'clouds_sparse': [], 'clouds_dense': [], 'labels': []}
+    for i, batch in enumerate(batches):
+        if i == n_batches:
+            break
+        sparse = _device_batch(batch, False)['cloud'][:, :, :sparse_size].contiguous()
+        dense, labels = model.upsample_many(sparse, n_points, return_labels=True, state=state)
+        parts['clouds_sparse'].append(sparse)
+        parts['clouds_dense'].append(dense)
+        parts['labels'].append(labels.to(torch.uint8))
+    if not parts['clouds_sparse']:
+        raise GwtfError('no batches: the iterable is empty')
+    return {k: torch.cat(v).contiguous() for k, v in parts.items()}
+
+
 def pairwise_CD(clouds1, clouds2, bs=2048):
     """Chamfer distance (sum of the two directed means) of every cloud of ``clouds1`` against every cloud of ``clouds2``
     (reference utils.py:90-117) -> (N1, N2) float32 on the device.  ``bs`` (the reference's chunk size) is accepted and ignored:

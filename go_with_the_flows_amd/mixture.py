@@ -138,6 +138,14 @@ class MixtureStack:
         eps = self.engines[0].couplings[0]._eps_value
         return pw, _lib.film_forward(g, pf, self.K * self.C, self.f, eps), eps
 
+    def _film_k(self, gk):
+        """_film from a (K, R, G) code table: component k's couplings are conditioned on gk[k] (one launch, gwtf_film_forward_k)."""
+        if gk.dim() != 3 or gk.shape[0] != self.K or gk.shape[2] != self.G:
+            raise _lib.GwtfError(f'the code table must be (K={self.K}, R, G={self.G}), got {tuple(gk.shape)}')
+        pw, pf = self.packed()
+        eps = self.engines[0].couplings[0]._eps_value
+        return pw, _lib.film_forward_k(gk, pf, self.C, self.f, eps), eps
+
     def forward_all(self, p, g, mode='inverse'):
         """Every component on every point -> (out, logdet), each (K,B,3,N).  Training / density path."""
         e0 = self.engines[0]
@@ -217,13 +225,14 @@ class MixtureStack:
         return e0
 
     def launch_routed(self, work, g, out=None, want_logdet=False):
-        """FiLM + the routed stack launch on a layout `_lib.mixture_route` left in `work` -> (out, logdet or None), each (S, 3, n)."""
+        """FiLM + the routed stack launch on a layout `_lib.mixture_route` left in `work` -> (out, logdet or None), each (S, 3, n).
+        g: (S, G) codes, or a (K, S, G) table with a code per component and row (`_lib.mixture_route_sweep`'s rows)."""
         e0 = self._routed_ready(g)
         S, n = work['labels'].shape
         if out is None:
             out = torch.empty(S, 3, n, device=g.device, dtype=torch.float32)
         logdet = torch.empty(S, 3, n, device=g.device, dtype=torch.float32) if want_logdet else None
-        pw, film, eps = self._film(g.contiguous().float())
+        pw, film, eps = (self._film_k if g.dim() == 3 else self._film)(g.contiguous().float())
         return _lib.stack_forward_routed(work, pw, film, out, logdet, self.K, self.C, self.f, e0.pattern0, eps)
 
     def forward_routed(self, z0, g, labels):

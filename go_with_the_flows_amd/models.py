@@ -501,6 +501,109 @@ class Flow_Mixture_Model(Local_Cond_RNVP_MC_Global_RNVP_VAE):
             return self.generate_many(g, n_points, return_labels, state=state)
         return self.sample_many(g, n_points, return_labels)
 
+    _SWEEP_WEIGHTS = tuple(float(w) for w in np.float32(np.arange(1, 10, 1) / 10))        # evaluating.py:340
+
+    def _sweep_constant(self, key, make, dev):
+        """A small device tensor built from host values once per (key, device): a captured call copies nothing from the host."""
+        cache = self.__dict__.setdefault('_sweep_constants', {})
+        if (key, str(dev)) not in cache:
+            cache[(key, str(dev))] = make().to(dev)
+        return cache[(key, str(dev))]
+
+    @torch.no_grad()
+    def interpolate_many(self, codes_a, codes_b, n_points, weights=None, flow_idx=None, return_labels=False, state=None, explicit=None,
+                         out=None):
+        """Latent sweeps between S pairs of codes in one pass (the reference's `--interpolation` / `--interpolate_one_flow`, whose code
+        it keeps inside a string literal, evaluating.py:268-382): row (s, t) decodes (1. - w_t) * codes_a[s] + w_t * codes_b[s]
+        (float32, that expression; weights: T values or a (T,) float32 device tensor, default np.arange(1, 10) / 10).  The T steps of
+        a shape SHARE their draws -- point i has the same label word and the same three normals at every step, those generate_many
+        draws for shape s at the same (seed, call) -- so every step is a sample of the model at its code and a point moves
+        continuously along the sweep.  The mixture logits of a row come from its own code.  flow_idx (components, None: all): only
+        these take the row's interpolated code, for their base Gaussian and their FiLM conditioning; every other component stays at
+        codes_a[s] (one_flow_decode(..., interpolated_codes | codes1, ...), evaluating.py:359-365).
+        The heads run once on the R = S * T codes (and once on codes_a with flow_idx); then one routing launch
+        (gwtf_mixture_route_sweep), one FiLM launch and one routed stack launch: no host round trip, capturable in a graph after one
+        eager call, every replay drawing fresh clouds; one call advances the state by one.  explicit: generate_many's keys, (S, ...)
+        tensors shared by the T rows of a shape.  out: the (S, T, 3, n) result tensor.
+        -> (S, T, 3, n_points)[, labels (S, T, n_points) in 1..K as float]."""
+        for t, name in ((codes_a, 'codes_a'), (codes_b, 'codes_b')):
+            if not torch.is_tensor(t) or t.dim() != 2:
+                raise GwtfError(f'{name} must be an (S, G) tensor')
+        G, K = self.g_latent_space_size, self.n_components
+        if codes_a.shape != codes_b.shape or codes_a.shape[1] != G or codes_a.shape[0] < 1:
+            raise GwtfError(f'codes_a and codes_b must both be (S, {G}), got {tuple(codes_a.shape)} and {tuple(codes_b.shape)}')
+        S, n, dev = codes_a.shape[0], int(n_points), codes_a.device
+        if codes_b.device != dev:
+            raise GwtfError(f'codes_a lives on {dev}, codes_b on {codes_b.device}')
+        if torch.is_tensor(weights):
+            if weights.dim() != 1 or weights.dtype != torch.float32:
+                raise GwtfError('weights must be a sequence of numbers or a one-dimensional float32 tensor')
+            T = weights.shape[0]
+        else:
+            weights = self._SWEEP_WEIGHTS if weights is None else tuple(float(w) for w in weights)
+            T = len(weights)
+        if T < 1:
+            raise GwtfError('weights is empty: a sweep has at least one step')
+        if flow_idx is not None:
+            flow_idx = tuple(sorted({int(k) for k in flow_idx}))
+            if any(k < 0 or k >= K for k in flow_idx):
+                raise GwtfError(f'flow_idx {list(flow_idx)} names components outside [0, {K})')
+        stack = self.mixture_stack()
+        stack._routed_ready(codes_a)
+        if dev.type != 'cuda':
+            raise GwtfError(f'the codes live on {dev}: generation runs on a HIP device only, there is no CPU path')
+        R = S * T
+        if out is None:
+            out = torch.empty(S, T, 3, n, device=dev, dtype=torch.float32)
+        elif tuple(out.shape) != (S, T, 3, n) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise GwtfError(f'out must be a contiguous float32 tensor of shape {(S, T, 3, n)} on {dev}')
+        ex = dict(explicit or {})
+        unknown = set(ex) - {'words', 'labels_in', 'normals', 'z0_in'}
+        if unknown:
+            raise GwtfError(f'explicit: unknown keys {sorted(unknown)}')
+        if state is None:
+            if getattr(self, '_generate_state', None) is None or self._generate_state.device != dev:
+                self._generate_state = make_state(0, dev)
+            state = self._generate_state
+        if torch.is_tensor(weights):
+            w = weights.to(dev)
+        else:
+            w = self._sweep_constant(('weights', weights), lambda: torch.tensor(weights, dtype=torch.float32), dev)
+        w = w.view(1, T, 1)
+        a, b = codes_a.float().unsqueeze(1), codes_b.float().unsqueeze(1)
+        codes = ((1. - w) * a + w * b).reshape(R, G)
+        logits = self.get_weights(codes).contiguous().float()
+
+        def base_rows(g):                                        # (rows or 1, 3) each
+            mu0, lv0 = self._base_gaussian(g)
+            return [t.expand(-1, self.p_latent_space_size, 1)[:, :, 0].float() for t in (mu0, lv0)]
+        mu0, lv0 = base_rows(codes)
+        g = codes
+        if flow_idx is not None:
+            # (K, R, .) tables: the chosen components at the row's code, the others at codes_a[s]
+            own = self._sweep_constant(('flow_idx', flow_idx, K),
+                                       lambda: torch.tensor([k in flow_idx for k in range(K)]), dev).view(K, 1, 1)
+            at_a = lambda t: t if t.shape[0] == 1 else t.unsqueeze(1).expand(S, T, t.shape[1]).reshape(R, t.shape[1])
+            mu0, lv0 = (torch.where(own, x.expand(R, 3).unsqueeze(0), at_a(y).expand(R, 3).unsqueeze(0))
+                        for x, y in zip((mu0, lv0), base_rows(codes_a.float())))
+            g = torch.where(own, codes.unsqueeze(0), at_a(codes_a.float()).unsqueeze(0))
+        work = stack._routed_work(R, n, dev)
+        _lib.mixture_route_sweep(work, group=T, logits=logits, mu0=mu0.contiguous(), lv0=lv0.contiguous(), state=state, **ex)
+        stack.launch_routed(work, g, out=out.view(R, 3, n))
+        if return_labels:
+            return out, (work['labels'] + 1).float().view(S, T, n)
+        return out
+
+    @torch.no_grad()
+    def upsample_many(self, clouds, n_points, return_labels=False, state=None):
+        """S sparse clouds (S, 3, N) -> S dense clouds of ``n_points`` points with a component label per point: the reference's
+        `--sampling` branch (`sample`, evaluating.py:384-457, kept inside a string literal there).  The codes are the posterior means
+        of the clouds (encode(...)['g_posterior_mus']), taken from the cloud encoder and the posterior head directly, so that --
+        unlike autoencode_many -- the call works in every ``model.mode``; the decoder step is ``generate_many``.
+        -> (S, 3, n_points)[, labels (S, n_points) in 1..K]."""
+        g = self.g_posterior(self._pooled_features(clouds))[0]
+        return self.generate_many(g, n_points, return_labels, state=state)
+
     def _decode_partitioned_many(self, z0, g_samples, labels):
         """z0 (S, 3, n) base samples, labels (S, n) numpy: point i of sample s through component labels[s, i] -> (S, 3, n)."""
         S, _, n = z0.shape

@@ -77,6 +77,13 @@ int gwtf_pack_weights_k(const float* raw, float* packed_w, float* packed_film,
  *   eps      the coupling's `eps` buffer (reference flows.py:21, 1e-6) */
 int gwtf_film_forward(const float* g, const float* packed_film, float* film_out, int B, int G, int C, int f, float eps,
                       void* stream);
+/* gwtf_film_forward over the C = K*Cper concatenated couplings of K components, every component conditioned on latent rows of its
+ * own (added without a version change): coupling c reads its B rows at g + (c / Cper) * g_stride_k, g_stride_k >= 0 floats from
+ * one component's [B][G] table to the next.  Stride 0 is gwtf_film_forward(C = K*Cper).  Same kernel body, instantiations, grid
+ * and arithmetic per (coupling, row): component k's part of film_out equals, bit for bit, what gwtf_film_forward writes there when
+ * it is run on table k.  GWTF_E_BADARG as for gwtf_film_forward, and for K < 1, Cper < 1 or a negative stride. */
+int gwtf_film_forward_k(const float* g, const float* packed_film, float* film_out, int B, int G, int K, int Cper, int f, float eps,
+                        long long g_stride_k, void* stream);
 
 /* Fused coupling stack: all C elementary couplings applied to every point, with the log-det
  * accumulation.  Replaces LocalCondRNVPDecoder.forward (lib/networks/decoders.py:61-79) ->
@@ -825,6 +832,43 @@ int gwtf_route_tiles(int n, int K, int P);
  * or P = 256 beyond f = 64. */
 int gwtf_mixture_route(const GwtfRouteArgs* args);
 int gwtf_stack_forward_routed(const GwtfRoutedStackArgs* args);
+
+/* Latent sweeps (added without a version change; no existing record, signature or kernel changed): R = S rows are decoded, row r
+ * taking the DRAWS of shape r / group -- T = group steps of a sweep between two latent codes share their label words and normals,
+ * so every step is a sample of the model at its own code and point i moves continuously along the sweep -- and, per component, a
+ * base Gaussian of its own, so that chosen components can follow the sweep while the others stay at one code.
+ *
+ * gwtf_mixture_route_sweep (csrc/gwtf_route.hip, the body of gwtf_mixture_route): one workgroup per ROW, then the same one-thread
+ * launch that stores call + 1 into state[1] (one advance per call, whatever R).
+ *   Draws: the Philox counter is (i, r / group, call lo, call hi | stream << 28), and words / labels_in / normals / z0_in hold
+ *   [S / group][...]: row r reads row r / group of each.  group = 1 draws what gwtf_mixture_route draws.
+ *   Per row: logits [R][K] -> thresholds and the component of every point by the rule above, from the row's own logits.
+ *   Base sample: z = eps * expf(0.5f * lv0) + mu0 with the three floats at mu0 + r * mu0_stride + k * mu0_stride_k for the point's
+ *   OWN component k (its label is known before the sample is formed; the K x 3 means and deviations of a row sit in LDS);
+ *   mu0_stride_k = 0: one base for all components, and with group = 1 every output bit is gwtf_mixture_route's.
+ *   Outputs: tile_comp, perm, zp, labels, thresholds as above for R rows; gwtf_stack_forward_routed takes them with S = R. */
+typedef struct GwtfRouteSweepArgs {
+  const float* logits;               /* [R][K]; NULL with labels_in */
+  const float* mu0;                  /* base mean / log-variance tables; NULL with z0_in */
+  const float* lv0;
+  long long* state;                  /* {seed, call} */
+  const int* words;                  /* explicit: [R / group][n] bits of the uint32 label words, or NULL */
+  const int* labels_in;              /* explicit: [R / group][n] components; takes precedence over words */
+  const float* normals;              /* explicit: [R / group][3][n] standard normals, or NULL */
+  const float* z0_in;                /* explicit: [R / group][3][n] base samples; takes precedence over normals */
+  int* thresholds;                   /* [R][K] or NULL */
+  int* tile_comp;                    /* [R][tiles] */
+  int* perm;                         /* [R][tiles * P] */
+  float* zp;                         /* [R][3][tiles * P] */
+  int* labels;                       /* [R][n] */
+  int S, n, K, P;                    /* S: the R rows */
+  int mu0_stride, lv0_stride;        /* floats from one row's values to the next: 3, or 0 for shared values */
+  int group;                         /* >= 1, divides S: rows per shape of draws */
+  int mu0_stride_k, lv0_stride_k;    /* floats from one component's table to the next, or 0: one base for all components */
+  void* stream;
+} GwtfRouteSweepArgs;
+/* GWTF_E_BADARG without a launch for everything gwtf_mixture_route refuses, group < 1, S % group != 0 and a negative stride. */
+int gwtf_mixture_route_sweep(const GwtfRouteSweepArgs* args);
 
 /* Image batches transformed on the device (csrc/gwtf_images.hip; added without a version change, no existing record or signature
  * moved): what ShapeNetAllDataset.__getitem__ (lib/datasets/datasets.py:173-222) and ComposeImageTransformation
