@@ -13,7 +13,8 @@ from .resnet import ResNet, BasicBlock, resnet18
 from .clouds import MeshStore, CloudStore, CloudTransform, DeviceCloudLoader, sample_clouds, sample_stored_clouds, make_state
 from .images import ImageStore, ImageTransform, DeviceSVRLoader, transform_images
 from .metrics import EvalFrame, clouds_to_eval_frame, chamfer_paired, paired_metrics
-from .evaluation import evaluate_generation, evaluate_autoencoding, evaluate_reconstruction, interpolate_clouds, upsample_clouds
+from .evaluation import (evaluate_generation, evaluate_autoencoding, evaluate_reconstruction, interpolate_clouds, upsample_clouds,
+                         segment_clouds, part_agreement)
 from ._lib import GwtfError
 
 __all__ = ['SharedDot', 'Swish', 'CondRealNVPFlow3D', 'CondRealNVPFlow3DTriple', 'LocalCondRNVPDecoder',
@@ -24,4 +25,4 @@ __all__ = ['SharedDot', 'Swish', 'CondRealNVPFlow3D', 'CondRealNVPFlow3DTriple',
            'resnet18', 'MeshStore', 'CloudStore', 'CloudTransform', 'DeviceCloudLoader', 'sample_clouds', 'sample_stored_clouds', 'make_state',
            'ImageStore', 'ImageTransform', 'DeviceSVRLoader', 'transform_images', 'EvalFrame', 'clouds_to_eval_frame',
            'chamfer_paired', 'paired_metrics', 'evaluate_generation', 'evaluate_autoencoding', 'evaluate_reconstruction',
-           'interpolate_clouds', 'upsample_clouds']
+           'interpolate_clouds', 'upsample_clouds', 'segment_clouds', 'part_agreement']

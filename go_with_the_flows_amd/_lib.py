@@ -133,6 +133,7 @@ _SIGNATURES = {
     'gwtf_chamfer_paired_partials': (ctypes.c_int, [ctypes.c_int] * 2),
     'gwtf_chamfer_paired': (ctypes.c_int, [_c_fp] * 3 + [ctypes.POINTER(ctypes.c_float)] + [ctypes.c_int] * 4 + [_c_fp]),
     'gwtf_paired_finalise': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 5 + [_c_fp]),
+    'gwtf_mixture_assign': (ctypes.c_int, [ctypes.c_void_p]),
 }
 
 PHASE_FWD_INIT, PHASE_FWD_A, PHASE_FWD_B, PHASE_BWD_A, PHASE_BWD_B, PHASE_BWD_C = range(6)
@@ -283,6 +284,13 @@ class EvalFrameArgs(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_void_p) for n in ('gen', 'ref', 'orig_s', 'orig_c', 'gen_out', 'ref_out')] +
                 [(n, ctypes.c_int) for n in ('B', 'n', 'm', 'n_scale', 'translate', 'row_scale', 'row_shift')] +
                 [('scale', ctypes.c_float), ('shift', ctypes.c_double * 3), ('stream', ctypes.c_void_p)])
+
+
+class AssignArgs(ctypes.Structure):
+    """GwtfAssignArgs of include/gwtf.h (per-point component posteriors of observed clouds): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('z', 'logdet', 'mu0', 'lv0', 'logits', 'parts', 'log_density', 'labels', 'confidence',
+                                                'resp', 'counts', 'invalid', 'table', 'skipped')] +
+                [(n, ctypes.c_int) for n in ('K', 'B', 'N', 'P')] + [('stream', ctypes.c_void_p)])
 
 
 class LoopState(ctypes.Structure):
@@ -590,6 +598,60 @@ def mixture_nll(z, logdet, mu0, lv0, logits, want_point_lse=False):
                                  _ptr(logits, 'logits'), _ptr(plse, 'point_lse'), _ptr(nll, 'nll_shape'), K, B, N,
                                  _stream(z)))
     return (nll, plse) if want_point_lse else nll
+
+
+ASSIGN_MAX_PARTS = 64                 # P of GwtfAssignArgs
+
+
+def mixture_assign(z, logdet, mu0, lv0, logits, want_confidence=True, want_resp=False, parts=None, n_parts=None, table=None,
+                   skipped=None, out=None):
+    """gwtf_mixture_assign on the current stream: the inputs of mixture_nll -> {'log_density' (B, N) float32, 'labels' (B, N) int32 in
+    [0, K) or -1, 'confidence' (B, N) float32, 'resp' (B, K, N) float32, 'counts' (B, K) int32, 'invalid' (B,) int32}, device tensors;
+    'confidence' / 'resp' are None when not wanted.  parts (B, N) int32 with n_parts = P in 1..64: the (label, part) contingency is
+    ADDED to table (K, P) int64 and the points left out to skipped (1,) int64 -- zeroed tensors are made when none are passed -- and
+    both are returned under 'table' / 'skipped'.  out: a dict as returned by an earlier call on the same shapes, whose tensors are
+    written instead of new ones (a captured call then allocates nothing)."""
+    if z.dim() != 4 or z.shape[2] != 3:
+        raise GwtfError(f'z must be (K, B, 3, N), got {tuple(z.shape)}')
+    K, B, _, N = z.shape
+    dev, f32, i32, i64 = z.device, torch.float32, torch.int32, torch.int64
+    for t, name, shape in ((logdet, 'logdet', (K, B, 3, N)), (mu0, 'mu0', (K, B, 3)), (lv0, 'lv0', (K, B, 3)), (logits, 'logits', (B, K))):
+        if tuple(t.shape) != shape or t.device != dev:
+            raise GwtfError(f'{name} must be {shape} on {dev}, got {tuple(t.shape)} on {t.device}')
+    ptrs = [_ptr(t, name) for t, name in ((z, 'z'), (logdet, 'logdet'), (mu0, 'mu0'), (lv0, 'lv0'), (logits, 'logits'))]
+    P = 0
+    if parts is not None:
+        if n_parts is None or not 1 <= int(n_parts) <= ASSIGN_MAX_PARTS:
+            raise GwtfError(f'parts needs n_parts in 1..{ASSIGN_MAX_PARTS}, got {n_parts}')
+        P = int(n_parts)
+        _explicit(parts, 'parts', (B, N), i32, dev)
+        if table is None:
+            table = torch.zeros(K, P, device=dev, dtype=i64)
+        if skipped is None:
+            skipped = torch.zeros(1, device=dev, dtype=i64)
+        _explicit(table, 'table', (K, P), i64, dev)
+        _explicit(skipped, 'skipped', (1,), i64, dev)
+    spec = {'log_density': ((B, N), f32, True), 'labels': ((B, N), i32, True), 'confidence': ((B, N), f32, want_confidence),
+            'resp': ((B, K, N), f32, want_resp), 'counts': ((B, K), i32, True), 'invalid': ((B,), i32, True)}
+    res = {}
+    for name, (shape, dtype, wanted) in spec.items():
+        if not wanted:
+            res[name] = None
+        elif out is not None:
+            if out.get(name) is None:
+                raise GwtfError(f'out has no {name!r}')
+            _explicit(out[name], f'out[{name!r}]', shape, dtype, dev)
+            res[name] = out[name]
+        else:
+            res[name] = torch.empty(shape, device=dev, dtype=dtype)
+    at = lambda t: None if t is None else t.data_ptr()
+    a = AssignArgs(*ptrs, at(parts), *(at(res[n]) for n in spec), at(table) if parts is not None else None,
+                   at(skipped) if parts is not None else None, K, B, N, P, _stream(z))
+    with torch.cuda.device(dev):
+        check(lib().gwtf_mixture_assign(ctypes.addressof(a)))
+    if parts is not None:
+        res['table'], res['skipped'] = table, skipped
+    return res
 
 
 def stack_plan(K, B, N, f, segments=None, word=None):

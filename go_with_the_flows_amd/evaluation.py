@@ -451,6 +451,80 @@ def upsample_clouds(model, batches, sparse_size, n_points, n_batches=10, state=N
     return {k: torch.cat(v).contiguous() for k, v in parts.items()}
 
 
+@torch.no_grad()
+def segment_clouds(model, batches, n_batches=None, parts_key=None, n_parts=None, want_resp=False):
+    """Label observed clouds by mixture component, on the device: per batch the codes are the posterior means of batch['cloud'] and
+    the labelled points are batch['eval_cloud'] (the pairing of evaluating.py:83-84), through Flow_Mixture_Model.assign_many.
+    ``batches``: device dicts with 'cloud' and 'eval_cloud' (DeviceCloudLoader), the first ``n_batches`` of them (None: all);
+    parts_key: batch[parts_key] is the (B, N) integer ground-truth part of every point of 'eval_cloud', one of ``n_parts``.
+    Nothing is read back inside the loop.
+    -> {'clouds' (M, 3, N) float32, 'labels' (M, N) uint8 holding label + 1 with 0 for an invalid point (the `t + 1` convention of the
+    reference's h5 `labels` datasets and of upsample_clouds), 'log_density' (M, N), 'confidence' (M, N) float32, 'counts' (M, K)
+    int32[, 'resp' (M, K, N)]}; with parts also 'table' (K, n_parts) int64, the (component, part) contingency over all batches --
+    part_agreement scores it -- and 'skipped' (1,) int64, the points outside it (invalid label or part outside [0, n_parts))."""
+    if n_batches is not None and n_batches < 1:
+        raise ValueError('n_batches must be positive')
+    if parts_key is not None and n_parts is None:
+        raise ValueError('parts_key needs n_parts')
+    keys = ('clouds', 'labels', 'log_density', 'confidence', 'counts') + (('resp',) if want_resp else ())
+    parts, table, skipped = {k: [] for k in keys}, None, None
+    for i, batch in enumerate(batches):
+        if i == n_batches:
+            break
+        batch = _device_batch(batch, False)
+        points = batch['eval_cloud'].contiguous()
+        gt = None
+        if parts_key is not None:
+            gt = batch[parts_key]
+            if not _on_device(gt) or gt.is_floating_point() or tuple(gt.shape) != (points.shape[0], points.shape[2]):
+                raise GwtfError(f'batch[{parts_key!r}] must be a (B, N) integer tensor on a HIP device')
+            gt = gt.to(torch.int32).contiguous()
+        res = model.assign_many(points, codes=_posterior_means(model, batch['cloud']), want_resp=want_resp, parts=gt, n_parts=n_parts,
+                                table=table, skipped=skipped)
+        table, skipped = res.get('table'), res.get('skipped')
+        parts['clouds'].append(points)
+        parts['labels'].append((res['labels'] + 1).to(torch.uint8))
+        for k in keys[2:]:
+            parts[k].append(res[k])
+    if not parts['clouds']:
+        raise GwtfError('no batches: the iterable is empty')
+    out = {k: torch.cat(v).contiguous() for k, v in parts.items()}
+    if parts_key is not None:
+        out['table'], out['skipped'] = table, skipped
+    return out
+
+
+def part_agreement(table):
+    """Agreement of an unsupervised labelling with ground-truth parts from their (K, P) contingency table (segment_clouds' 'table'; a
+    device tensor is read once), host-side in float64.  -> {'purity', 'nmi', 'miou', 'mapping'}:
+      mapping[k] = argmax_p table[k, p], the lowest p on a tie: the part component k stands for
+      purity     = sum_k max_p table[k, p] / sum(table)
+      nmi        = I(K; P) / sqrt(H(K) H(P)) in nats, 0 when either entropy is 0
+      miou       = mean over the parts with a ground-truth point of TP_p / (GT_p + Pred_p - TP_p), a point predicted as mapping[label]
+    An all-zero table gives NaN for the three values."""
+    t = np.asarray(table.detach().cpu() if torch.is_tensor(table) else table).astype(np.float64)
+    if t.ndim != 2:
+        raise ValueError(f'table must be (K, P), got {t.shape}')
+    mapping = t.argmax(1)
+    total = t.sum()
+    if total == 0:
+        return {'purity': float('nan'), 'nmi': float('nan'), 'miou': float('nan'), 'mapping': mapping}
+    purity = t.max(1).sum() / total
+    pk, pp, joint = t.sum(1) / total, t.sum(0) / total, t / total
+    entr = lambda p: float(-(p[p > 0] * np.log(p[p > 0])).sum())
+    hk, hp = entr(pk), entr(pp)
+    nz = joint > 0
+    info = float((joint[nz] * np.log(joint[nz] / np.outer(pk, pp)[nz])).sum())
+    nmi = info / np.sqrt(hk * hp) if hk > 0 and hp > 0 else 0.0
+    P = t.shape[1]
+    confusion = np.zeros((P, P))                                   # [predicted part, true part]
+    np.add.at(confusion, mapping, t)
+    gt, pr, tp = confusion.sum(0), confusion.sum(1), np.diag(confusion)
+    seen = gt > 0
+    miou = float((tp[seen] / (gt[seen] + pr[seen] - tp[seen])).mean())
+    return {'purity': float(purity), 'nmi': float(nmi), 'miou': miou, 'mapping': mapping}
+
+
 def pairwise_CD(clouds1, clouds2, bs=2048):
     """Chamfer distance (sum of the two directed means) of every cloud of ``clouds1`` against every cloud of ``clouds2``
     (reference utils.py:90-117) -> (N1, N2) float32 on the device.  ``bs`` (the reference's chunk size) is accepted and ignored:

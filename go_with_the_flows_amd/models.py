@@ -604,6 +604,38 @@ class Flow_Mixture_Model(Local_Cond_RNVP_MC_Global_RNVP_VAE):
         g = self.g_posterior(self._pooled_features(clouds))[0]
         return self.generate_many(g, n_points, return_labels, state=state)
 
+    @torch.no_grad()
+    def assign_many(self, clouds, codes=None, want_resp=False, parts=None, n_parts=None, table=None, skipped=None, out=None):
+        """The inference direction of the mixture for B observed clouds (B, 3, N) on the device: which component explains each point,
+        and how likely the point is.  For every point the responsibility r_k = softmax_k(log w_k + log p_k(x | code)) of the K
+        components (the per-component terms of FlowMixtureNLL, losses.py:101-122) reduced by one launch (csrc/gwtf_assign.hip) behind
+        the batched density launch.  codes (B, G): the latent codes the components are conditioned on; default the posterior means of
+        ``clouds``, taken as upsample_many takes them, so that the call works in every ``model.mode`` -- codes of OTHER clouds label
+        held-out points of the same shapes.
+        -> {'log_density' (B, N) float32 = logsumexp_k, 'labels' (B, N) int32 in [0, K) (argmax, lowest k on a tie; -1 where the
+        log-density is not finite; the type forward_routed's labels take), 'confidence' (B, N) = r of the label, 'resp' (B, K, N) or
+        None, 'counts' (B, K) int32, 'invalid' (B,) int32}.  parts (B, N) int32 with n_parts: the (label, part) contingency is ADDED
+        to table (K, n_parts) int64 and the points left out to skipped (1,) int64, both returned as well (made when not passed).
+        out: the dict of an earlier call, written in place.  After one eager call the same call with out= can be captured in a graph."""
+        if _stack_training(self):
+            raise NotImplementedError('assign_many is an evaluation path (eval-mode BatchNorm in the decoders); call .eval()')
+        if not torch.is_tensor(clouds) or clouds.device.type != 'cuda':
+            raise GwtfError('clouds must live on a HIP device; there is no CPU path')
+        if clouds.dim() != 3 or clouds.shape[1] != 3:
+            raise GwtfError(f'clouds must be (B, 3, N), got {tuple(clouds.shape)}')
+        B, K, P = clouds.shape[0], self.n_components, self.p_latent_space_size
+        if codes is None:
+            codes = self.g_posterior(self._pooled_features(clouds))[0]
+        elif not torch.is_tensor(codes) or codes.device != clouds.device or tuple(codes.shape) != (B, self.g_latent_space_size):
+            raise GwtfError(f'codes must be ({B}, {self.g_latent_space_size}) on {clouds.device}')
+        logits = self.get_weights(codes).contiguous().float()
+        m, v = self._base_gaussian(codes)
+        mu0 = m.expand(B, P, 1)[:, :, 0].unsqueeze(0).expand(K, B, P).contiguous().float()
+        lv0 = v.expand(B, P, 1)[:, :, 0].unsqueeze(0).expand(K, B, P).contiguous().float()
+        z, logdet = self.mixture_stack().forward_all(clouds, codes, mode='inverse')
+        return _lib.mixture_assign(z, logdet, mu0, lv0, logits, want_resp=want_resp, parts=parts, n_parts=n_parts, table=table,
+                                   skipped=skipped, out=out)
+
     def _decode_partitioned_many(self, z0, g_samples, labels):
         """z0 (S, 3, n) base samples, labels (S, n) numpy: point i of sample s through component labels[s, i] -> (S, 3, n)."""
         S, _, n = z0.shape
@@ -705,6 +737,27 @@ class Flow_Mixture_SVR_Model(Flow_Mixture_Model):
         if state is not None:
             return self.generate_many(g, n_points, return_labels, state=state)
         return self.sample_many(g, n_points, return_labels)
+
+    @torch.no_grad()
+    def assign_many(self, clouds, images=None, codes=None, **kwargs):
+        """Flow_Mixture_Model.assign_many with the codes of single-view reconstruction: with ``images`` (B, 4, H, W) the codes are the
+        ones reconstruct_many decodes from (the g0_prior means of the image features through the prior flow direct).  Exactly one of
+        ``images`` and ``codes``: this model has no cloud-only route to a code outside training."""
+        if (images is None) == (codes is None):
+            raise GwtfError('assign_many needs exactly one of images and codes')
+        if images is not None:
+            if _stack_training(self):
+                raise NotImplementedError('assign_many is an evaluation path (eval-mode BatchNorm in the decoders); call .eval()')
+            if not torch.is_tensor(images) or images.device.type != 'cuda' or not torch.is_tensor(clouds) or clouds.device != images.device:
+                raise GwtfError('clouds and images must live on one HIP device; there is no CPU path')
+            mus, _ = self.g0_prior(self.img_encoder(images))
+            codes = self.g_prior(mus, mode='direct')[0][-1]
+        return super().assign_many(clouds, codes=codes, **kwargs)
+
+
+def _stack_training(model):
+    """Whether the decoders' BatchNorm is in train mode (what the routed and the assignment paths refuse before any launch)."""
+    return model.mixture_stack().engines[0].couplings[0].training
 
 
 def _restack(tensors):

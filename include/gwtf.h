@@ -1103,6 +1103,47 @@ int gwtf_chamfer_paired(const float* a, const float* b, float* partials, const f
 int gwtf_paired_finalise(const float* partials, const float* emd_cost, float* cd, float* cdl, float* cdr, float* emd, float* f1,
                          double* meter, int meter_head, int n_thr, int B, int n, int m, void* stream);
 
+/* Per-point component posteriors of observed clouds (csrc/gwtf_assign.hip; added without a version change, no existing record or
+ * signature moved): the inference direction of the mixture.  Inputs are exactly what gwtf_mixture_nll reads, and per shape b, point n,
+ * component k the same quantity in the same float32 expression (lib/networks/losses.py:101-122, its log(exp(logit)) - logsumexp weight
+ * included):
+ *   lp_k = -0.5 * sum_d [ lv0 + logdet + (z - mu0)^2 / exp(lv0) ] - 1.5 * log(2 pi) + log w_bk
+ *   log_density = logsumexp_k lp_k                 (what point_lse of gwtf_mixture_nll holds)
+ *   labels      = argmax_k lp_k in [0, K), the LOWEST k on an exact tie; -1 (invalid) when log_density is not finite: a NaN anywhere in
+ *                 the point's lp_k (log_density is then NaN), every component at -inf (log_density -inf), an lp of +inf
+ *   confidence  = exp(lp_label - log_density), 0 where the label is -1
+ *   resp[k]     = exp(lp_k - log_density), NaN in every k where the label is -1; resp of the label equals confidence bit for bit.
+ *                 With resp NULL z and logdet are read exactly once, with it twice
+ *   counts      = points per (shape, component), invalid = points labelled -1 per shape: WRITTEN by the call (cleared on the stream,
+ *                 then added to with integer atomics)
+ *   table       = the contingency of (label, part) over every point with a label >= 0 and a part in [0, P), ADDED TO and never cleared
+ *                 (a set is folded in batch by batch, as counts of gwtf_voxel_occupancy is); skipped += the points left out
+ * Integer atomics only, no float atomic anywhere: the same inputs give the same bits in every output on every call.  16-byte loads when
+ * N is a multiple of 4 and z, logdet, parts and the per-point outputs are 16-byte aligned, float by float otherwise -- the same
+ * arithmetic per point, hence the same bits.  Everything is enqueued on `stream`; no allocation, no synchronisation. */
+typedef struct GwtfAssignArgs {
+  const float* z;                    /* [K][B][3][N] */
+  const float* logdet;               /* [K][B][3][N] */
+  const float* mu0;                  /* [K][B][3] */
+  const float* lv0;                  /* [K][B][3] */
+  const float* logits;               /* [B][K] */
+  const int* parts;                  /* [B][N] ground-truth part of every point, or NULL */
+  float* log_density;                /* [B][N] */
+  int* labels;                       /* [B][N]; int32 is what labels_in of GwtfRouteArgs takes */
+  float* confidence;                 /* [B][N], or NULL */
+  float* resp;                       /* [B][K][N], or NULL */
+  int* counts;                       /* [B][K], written; or NULL */
+  int* invalid;                      /* [B], written; or NULL */
+  long long* table;                  /* [K][P], added to; read only with parts */
+  long long* skipped;                /* [1], added to; or NULL; read only with parts */
+  int K, B, N;
+  int P;                             /* 1..64 with parts */
+  void* stream;
+} GwtfAssignArgs;
+/* GWTF_E_BADARG without a launch: a NULL record or required pointer (the five inputs, log_density, labels), K outside 1..64, B or N
+ * below 1, with parts a P outside 1..64 or a NULL table.  GWTF_E_UNSUPPORTED: B * ceil(N / 512) beyond an int. */
+int gwtf_mixture_assign(const GwtfAssignArgs* args);
+
 #ifdef __cplusplus
 }
 #endif
