@@ -5,6 +5,7 @@ from .decoders import LocalCondRNVPDecoder
 from .mixture import MixtureStack, flow_mixture_nll
 from . import optim
 from . import metrics
+from . import render
 from . import evaluation
 from .encoders import PointNetCloudEncoder, FeatureEncoder, WeightsEncoder
 from .prior import RealNVPFlow, RealNVPFlowCouple, GlobalRNVPDecoder, GaussianFlowNLL, GaussianEntropy
@@ -14,7 +15,8 @@ from .clouds import MeshStore, CloudStore, CloudTransform, DeviceCloudLoader, sa
 from .images import ImageStore, ImageTransform, DeviceSVRLoader, transform_images
 from .metrics import EvalFrame, clouds_to_eval_frame, chamfer_paired, paired_metrics
 from .evaluation import (evaluate_generation, evaluate_autoencoding, evaluate_reconstruction, interpolate_clouds, upsample_clouds,
-                         segment_clouds, part_agreement)
+                         segment_clouds, part_agreement, reconstruction_figure, sweep_figure, segmentation_figure)
+from .render import PALETTE, GROUND_TRUTH_RGB, view_matrix, fit_views, render_clouds, save_png
 from ._lib import GwtfError
 
 __all__ = ['SharedDot', 'Swish', 'CondRealNVPFlow3D', 'CondRealNVPFlow3DTriple', 'LocalCondRNVPDecoder',
@@ -25,4 +27,5 @@ __all__ = ['SharedDot', 'Swish', 'CondRealNVPFlow3D', 'CondRealNVPFlow3DTriple',
            'resnet18', 'MeshStore', 'CloudStore', 'CloudTransform', 'DeviceCloudLoader', 'sample_clouds', 'sample_stored_clouds', 'make_state',
            'ImageStore', 'ImageTransform', 'DeviceSVRLoader', 'transform_images', 'EvalFrame', 'clouds_to_eval_frame',
            'chamfer_paired', 'paired_metrics', 'evaluate_generation', 'evaluate_autoencoding', 'evaluate_reconstruction',
-           'interpolate_clouds', 'upsample_clouds', 'segment_clouds', 'part_agreement']
+           'interpolate_clouds', 'upsample_clouds', 'segment_clouds', 'part_agreement', 'render', 'PALETTE', 'GROUND_TRUTH_RGB',
+           'view_matrix', 'fit_views', 'render_clouds', 'save_png', 'reconstruction_figure', 'sweep_figure', 'segmentation_figure']

@@ -134,6 +134,7 @@ _SIGNATURES = {
     'gwtf_chamfer_paired': (ctypes.c_int, [_c_fp] * 3 + [ctypes.POINTER(ctypes.c_float)] + [ctypes.c_int] * 4 + [_c_fp]),
     'gwtf_paired_finalise': (ctypes.c_int, [_c_fp] * 8 + [ctypes.c_int] * 5 + [_c_fp]),
     'gwtf_mixture_assign': (ctypes.c_int, [ctypes.c_void_p]),
+    'gwtf_render_splats': (ctypes.c_int, [ctypes.c_void_p]),
 }
 
 PHASE_FWD_INIT, PHASE_FWD_A, PHASE_FWD_B, PHASE_BWD_A, PHASE_BWD_B, PHASE_BWD_C = range(6)
@@ -291,6 +292,15 @@ class AssignArgs(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_void_p) for n in ('z', 'logdet', 'mu0', 'lv0', 'logits', 'parts', 'log_density', 'labels', 'confidence',
                                                 'resp', 'counts', 'invalid', 'table', 'skipped')] +
                 [(n, ctypes.c_int) for n in ('K', 'B', 'N', 'P')] + [('stream', ctypes.c_void_p)])
+
+
+class RenderArgs(ctypes.Structure):
+    """GwtfRenderArgs of include/gwtf.h (labelled clouds drawn into the cells of a contact sheet): same field order."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ('clouds', 'labels', 'palette', 'view', 'rgb', 'index', 'depth', 'skipped')] +
+                [(n, ctypes.c_int) for n in ('B', 'N', 'P', 'label_base', 'view_stride', 'H', 'W', 'radius_q', 'fog', 'sheet_h', 'sheet_w',
+                                             'cols', 'cell0', 'cell_step')] +
+                [('near', ctypes.c_float), ('inv_range', ctypes.c_float), ('invalid_rgb', ctypes.c_ubyte * 3),
+                 ('background_rgb', ctypes.c_ubyte * 3), ('stream', ctypes.c_void_p)])
 
 
 class LoopState(ctypes.Structure):
@@ -652,6 +662,41 @@ def mixture_assign(z, logdet, mu0, lv0, logits, want_confidence=True, want_resp=
     if parts is not None:
         res['table'], res['skipped'] = table, skipped
     return res
+
+
+RENDER_MAX_PALETTE, RENDER_MAX_RADIUS_Q = 256, 16 * 64        # P and radius_q of GwtfRenderArgs
+
+
+def render_splats(clouds, labels, palette, view, rgb, H, W, *, label_base=0, radius_q=24, near=0.0, inv_range=0.0, fog=0, cols=1,
+                  cell0=0, cell_step=1, invalid_rgb=(0, 0, 0), background_rgb=(255, 255, 255), index=None, depth=None, skipped=None):
+    """gwtf_render_splats on the current stream: clouds (B, 3, N) float32, labels (B, N) int32 or None, palette (P, 3) uint8, view
+    (3, 4) -- one for all images -- or (B, 3, 4) float32, drawn into the cells cell0 + b * cell_step (H x W pixels each, `cols` per sheet
+    row) of rgb (3, sheet_h, sheet_w) uint8.  index (B, H, W) int32, depth (B, H, W) float32, skipped (B,) int32: optional outputs.
+    Every tensor lives on the device of `clouds`; nothing is allocated or read back.  Rules: include/gwtf.h (GwtfRenderArgs)."""
+    if not torch.is_tensor(clouds) or clouds.dim() != 3 or clouds.shape[1] != 3:
+        raise GwtfError(f'clouds must be a (B, 3, N) tensor, got {tuple(getattr(clouds, "shape", ()))}')
+    B, _, N = clouds.shape
+    dev, f32, i32, u8 = clouds.device, torch.float32, torch.int32, torch.uint8
+    p_clouds = _ptr(clouds, 'clouds')
+    H, W = int(H), int(W)
+    if palette.dim() != 2 or palette.shape[1] != 3 or not 1 <= palette.shape[0] <= RENDER_MAX_PALETTE:
+        raise GwtfError(f'palette must be (P, 3) with P in 1..{RENDER_MAX_PALETTE}, got {tuple(palette.shape)}')
+    if tuple(view.shape) not in ((3, 4), (B, 3, 4)):
+        raise GwtfError(f'view must be (3, 4) or ({B}, 3, 4), got {tuple(view.shape)}')
+    if rgb.dim() != 3 or rgb.shape[0] != 3:
+        raise GwtfError(f'rgb must be (3, sheet_h, sheet_w), got {tuple(rgb.shape)}')
+    a = RenderArgs(clouds=p_clouds, labels=_explicit(labels, 'labels', (B, N), i32, dev),
+                   palette=_explicit(palette, 'palette', palette.shape, u8, dev), view=_explicit(view, 'view', view.shape, f32, dev),
+                   rgb=_explicit(rgb, 'rgb', rgb.shape, u8, dev), index=_explicit(index, 'index', (B, H, W), i32, dev),
+                   depth=_explicit(depth, 'depth', (B, H, W), f32, dev), skipped=_explicit(skipped, 'skipped', (B,), i32, dev),
+                   B=B, N=N, P=palette.shape[0], label_base=int(label_base), view_stride=12 if view.dim() == 3 else 0, H=H, W=W,
+                   radius_q=int(radius_q), fog=int(fog), sheet_h=rgb.shape[1], sheet_w=rgb.shape[2], cols=int(cols), cell0=int(cell0),
+                   cell_step=int(cell_step), near=float(near), inv_range=float(inv_range),
+                   invalid_rgb=(ctypes.c_ubyte * 3)(*[int(c) for c in invalid_rgb]),
+                   background_rgb=(ctypes.c_ubyte * 3)(*[int(c) for c in background_rgb]), stream=_stream(clouds))
+    with torch.cuda.device(dev):
+        check(lib().gwtf_render_splats(ctypes.addressof(a)))
+    return rgb
 
 
 def stack_plan(K, B, N, f, segments=None, word=None):

@@ -11,6 +11,9 @@ all-pairs matrices come from metrics.chamfer_directed / metrics.emd_cost_pairs (
 one directed pass, every F1 threshold comes out of the same pass), and the result dictionaries are those of compute_all_metrics.
 pairwise_CD / COV / MMD / KNN mirror lib/networks/utils.py:90-144.
 
+reconstruction_figure / sweep_figure / segmentation_figure are the qualitative outputs (lib/visualization/utils.py:41-61 and its
+kin) as contact sheets drawn on the device by render.render_clouds.
+
 evaluate_generation / evaluate_autoencoding / evaluate_reconstruction are the three branches of the reference's evaluate
 (evaluating.py:13-266) in one call each, on the device; the two paired ones run on metrics.clouds_to_eval_frame and
 metrics.paired_metrics (cloud i against cloud i, one Chamfer pass for CD and every F1 threshold, sums kept on the device).
@@ -20,6 +23,7 @@ import torch
 from scipy.stats import entropy
 
 from . import metrics as _metrics
+from . import render as _render
 from ._lib import GwtfError
 from .metrics import distChamferCUDA, emd_approx, f_score  # noqa: F401  (re-exported: evaluating.py imports them from here)
 
@@ -492,6 +496,101 @@ def segment_clouds(model, batches, n_batches=None, parts_key=None, n_parts=None,
     if parts_key is not None:
         out['table'], out['skipped'] = table, skipped
     return out
+
+
+# ---- figures: contact sheets drawn on the device (render.py, csrc/gwtf_render.hip) ------------------------------------------------------
+_FIGURE_OWNS = ('views', 'out', 'cols', 'cell0', 'cell_step', 'label_base', 'want_index', 'want_depth', 'skipped')
+
+
+def _figure_options(render):
+    """(size, angles, margin, the options handed on to every render_clouds call of a figure)."""
+    taken = [k for k in _FIGURE_OWNS if k in render]
+    if taken:
+        raise GwtfError(f'a figure places its own cells: {taken} cannot be passed')
+    size = tuple(int(v) for v in render.get('size', (256, 256)))
+    return size, render.get('angles', _render.ANGLES), render.get('margin', 0.05), dict(render, size=size)
+
+
+def _column(sheet, clouds, labels, views, column, n_cols, opts, **more):
+    """One render_clouds call: cloud b into row b, column `column` of a sheet with n_cols columns."""
+    _render.render_clouds(clouds, labels, views=views, out=sheet, cols=n_cols, cell0=column, cell_step=n_cols, **dict(opts, **more))
+
+
+@torch.no_grad()
+def reconstruction_figure(model, batch, n_points, nr_samples=5, state=None, **render):
+    """The reference's GT_vs_RECONSTRUCTION figure (add_figures_reconstruction_tb / add_svr_reconstruction_tb,
+    lib/visualization/utils.py:41-61, called from training.py:147-167 and :269-291) as an image tensor, on the device.  ``batch``: one
+    device dict of a loader; its first ``nr_samples`` shapes make the rows.  Column 0: batch['eval_cloud'] in one colour
+    (render.GROUND_TRUTH_RGB); column 1: model.autoencode_many(batch['cloud'], n_points, return_labels=True, state=state) -- for a
+    Flow_Mixture_SVR_Model reconstruct_many(batch['image'], ...) -- coloured by component; for the SVR model column 2: channels 1:4
+    of the input image, clipped to [0, 1] as imshow clips floats and resampled to the cell (nearest).  Both clouds of a row share the
+    view fitted to the ground truth (render.fit_views).  render: size, radius, fog, palette, angles, margin, background, invalid of
+    render.render_clouds.  Nothing is read back.
+    -> (3, rows * H, n_cols * W) uint8: SummaryWriter.add_image('GT_vs_RECONSTRUCTION', sheet, epoch) takes it as it is."""
+    size, angles, margin, opts = _figure_options(render)
+    svr = hasattr(model, 'reconstruct_many')
+    batch = _device_batch(batch, svr)
+    S = min(int(nr_samples), batch['eval_cloud'].shape[0])
+    if S < 1:
+        raise GwtfError('nr_samples must be positive')
+    gt = batch['eval_cloud'][:S].contiguous()
+    if svr:
+        recon, labels = model.reconstruct_many(batch['image'][:S].contiguous(), n_points, return_labels=True, state=state)
+    else:
+        recon, labels = model.autoencode_many(batch['cloud'][:S].contiguous(), n_points, return_labels=True, state=state)
+    n_cols = 3 if svr else 2
+    sheet = _render.new_sheet(S, n_cols, size, gt.device, opts.get('background', _render.BACKGROUND_RGB))
+    views = _render.fit_views(gt, angles, size, margin)
+    _column(sheet, gt, None, views, 0, n_cols, opts, palette=np.array([_render.GROUND_TRUTH_RGB], np.uint8))
+    _column(sheet, recon, labels, views, 1, n_cols, opts, label_base=1)
+    if svr:
+        H, W = size
+        img = torch.nn.functional.interpolate(batch['image'][:S, 1:4].float(), size=(H, W), mode='nearest')
+        img = (img.clamp(0, 1) * 255).round().to(torch.uint8)                            # (S, 3, H, W)
+        sheet.view(3, S, H, n_cols, W)[:, :, :, 2, :] = img.permute(1, 0, 2, 3)
+    return sheet
+
+
+@torch.no_grad()
+def sweep_figure(out, **render):
+    """The dict interpolate_clouds returns as one sheet of S rows: 'clouds1' in one colour, the T steps of 'interpolations' coloured
+    by 'labels' (1..K), 'clouds2' in one colour -- T + 2 columns.  One view per row, fitted to 'clouds1', so that a row shows the
+    shape moving inside a fixed window.  render: as for reconstruction_figure.  -> (3, S * H, (T + 2) * W) uint8."""
+    size, angles, margin, opts = _figure_options(render)
+    for k in ('clouds1', 'clouds2', 'interpolations', 'labels'):
+        if k not in out or not _on_device(out[k]):
+            raise GwtfError(f"sweep_figure needs out[{k!r}] on a HIP device (the dict interpolate_clouds returns)")
+    c1, c2, steps, labels = out['clouds1'], out['clouds2'], out['interpolations'], out['labels']
+    S, T = steps.shape[0], steps.shape[3]
+    n_cols = T + 2
+    sheet = _render.new_sheet(S, n_cols, size, c1.device, opts.get('background', _render.BACKGROUND_RGB))
+    views = _render.fit_views(c1, angles, size, margin)
+    one = np.array([_render.GROUND_TRUTH_RGB], np.uint8)
+    _column(sheet, c1, None, views, 0, n_cols, opts, palette=one)
+    for t in range(T):
+        _column(sheet, steps[:, :, :, t], labels[:, :, t], views, 1 + t, n_cols, opts, label_base=1)
+    _column(sheet, c2, None, views, n_cols - 1, n_cols, opts, palette=one)
+    return sheet
+
+
+@torch.no_grad()
+def segmentation_figure(clouds, labels, parts=None, label_base=None, **render):
+    """Predicted components beside ground-truth parts: row b shows clouds[b] (B, 3, N) coloured by labels[b] (B, N) and, with
+    ``parts`` (B, N), by parts[b] (0-based; a negative part takes the invalid colour).  label_base: None takes the convention from
+    the dtype -- 1 for uint8 (segment_clouds' 'labels': label + 1, 0 invalid), 0 otherwise (assign_many's int32 with -1 invalid).
+    Both columns share the view fitted to the cloud.  -> (3, B * H, n_cols * W) uint8, n_cols 2 with parts and 1 without."""
+    size, angles, margin, opts = _figure_options(render)
+    if not _on_device(clouds) or not _on_device(labels) or (parts is not None and not _on_device(parts)):
+        raise GwtfError('segmentation_figure needs clouds, labels and parts on a HIP device; there is no CPU path')
+    if label_base is None:
+        label_base = 1 if labels.dtype == torch.uint8 else 0
+    n_cols = 1 if parts is None else 2
+    sheet = _render.new_sheet(clouds.shape[0], n_cols, size, clouds.device, opts.get('background', _render.BACKGROUND_RGB))
+    views = _render.fit_views(clouds, angles, size, margin)
+    _column(sheet, clouds, labels, views, 0, n_cols, opts, label_base=label_base)
+    if parts is not None:
+        _column(sheet, clouds, parts, views, 1, n_cols, opts, label_base=0)
+    return sheet
 
 
 def part_agreement(table):

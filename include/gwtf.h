@@ -1144,6 +1144,53 @@ typedef struct GwtfAssignArgs {
  * below 1, with parts a P outside 1..64 or a NULL table.  GWTF_E_UNSUPPORTED: B * ceil(N / 512) beyond an int. */
 int gwtf_mixture_assign(const GwtfAssignArgs* args);
 
+/* Labelled point clouds drawn into the cells of a contact sheet (csrc/gwtf_render.hip; added without a version change, no existing
+ * record or signature moved): B clouds, one cell of H x W pixels each, opaque depth-tested discs coloured by label.  Every step is
+ * integer arithmetic behind a float32 projection whose roundings are fixed, so that a restatement reproduces every output bit:
+ *   projection  row r of the image's view M (view + b * view_stride): t_r = ((M[r][0]*x + M[r][1]*y) + M[r][2]*z) + M[r][3], every
+ *               product and sum rounded to float32 on its own (no fused multiply-add).  u = t_0, v = t_1 in pixels of the cell: pixel
+ *               (i, j) covers [j, j+1) x [i, i+1), row 0 at the top.  d = t_2 + 0.0f (so -0 is +0); a smaller d is nearer
+ *   rejected    a point with a non-finite u, v or d draws nothing and is counted in skipped[b]; a point whose disc cannot touch the
+ *               cell draws nothing and is not counted (told in float32, before any conversion to an integer)
+ *   footprint   U = (int)floorf(u * 16.0f), V likewise.  Pixel (V >> 4, U >> 4) is always covered; pixel (i, j) is also covered when
+ *               (16 j + 8 - U)^2 + (16 i + 8 - V)^2 <= radius_q^2.  The depth is flat over the disc
+ *   winner      per pixel the smallest 64-bit key (ord(d) << 32) | n, ord the order-preserving map of float32 bits to uint32 (all bits
+ *               of a negative value flipped, the sign bit of a non-negative one): the nearest point, the lowest n on equal depth
+ *   colour      l = labels[b][n] - label_base: invalid_rgb when l < 0, else palette[l % P]; palette[0] with labels NULL.  Depth cue:
+ *               f = floorf(((d - near) * inv_range) * 256.0f) (unfused), q = 0 for f <= 0 or NaN, 255 for f >= 255, else (int)f;
+ *               w = 256 - ((fog * q) >> 8); every channel is (c * w) >> 8 -- unchanged with fog = 0
+ *   cell        image b goes to cell c = cell0 + b * cell_step of the sheet, origin ((c / cols) * H, (c % cols) * W)
+ *   rgb         EVERY pixel of the B cells is written (background_rgb where nothing was drawn): no clear is needed.  Pixels of the
+ *               sheet outside these cells are not touched
+ *   index       the winning n, -1 for background;  depth: its d, +inf for background;  skipped: WRITTEN by the call
+ * One launch, no scratch buffer, no global atomic, no float atomic: the same inputs give the same bits on every call.  Everything is
+ * enqueued on `stream`; no allocation, no synchronisation. */
+typedef struct GwtfRenderArgs {
+  const float* clouds;               /* [B][3][N] */
+  const int* labels;                 /* [B][N], or NULL */
+  const unsigned char* palette;      /* [P][3] */
+  const float* view;                 /* [B][3][4] (view_stride 12) or [3][4] (view_stride 0) */
+  unsigned char* rgb;                /* [3][sheet_h][sheet_w] */
+  int* index;                        /* [B][H][W], or NULL */
+  float* depth;                      /* [B][H][W], or NULL */
+  int* skipped;                      /* [B], written; or NULL */
+  int B, N, P;
+  int label_base;                    /* 1 for the generators' labels, 0 for those of gwtf_mixture_assign */
+  int view_stride;                   /* 0 or 12 floats */
+  int H, W;                          /* the cell */
+  int radius_q;                      /* disc radius in 1/16 pixel, 0..1024 */
+  int fog;                           /* 0..256 */
+  int sheet_h, sheet_w, cols, cell0, cell_step;
+  float near, inv_range;
+  unsigned char invalid_rgb[3], background_rgb[3];
+  void* stream;
+} GwtfRenderArgs;
+/* GWTF_E_BADARG without a launch: a NULL record or required pointer (clouds, palette, view, rgb), B, N, H or W below 1, P outside
+ * 1..256, view_stride not 0 or 12, radius_q outside 0..1024, fog outside 0..256, cols below 1, a cell that does not lie inside the
+ * sheet (cell0 or cell_step negative included), cell_step 0 with B above 1 (two images in one cell).  GWTF_E_UNSUPPORTED: H or W
+ * above 2^20, B * ceil(H / 64) * ceil(W / 64) beyond an int. */
+int gwtf_render_splats(const GwtfRenderArgs* args);
+
 #ifdef __cplusplus
 }
 #endif
